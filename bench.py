@@ -9,9 +9,14 @@ CRC32C, CRC init 0, bytes = little-endian splitmix64 stream seed 42, generated o
 shard across ranks with no data-path collective (weak scaling); the only collectives are the
 timing barriers, the max-over-ranks reduction and the gather of per-rank timings.
 
-Rank 0 prints ONE JSON line with ``roofline`` (dominant kernel, HIP-event timed on its own
-stream) and, at N=1, ``cpu_baseline`` (the reference's own circe crc32c() compiled from
-/root/reference into oracle/_ref, timed on the host cores over a bounded sample).
+A plain run sets up, warms up, times the K steps and prints: rank 0 prints ONE JSON line with
+``ms_per_step`` (wall time of the timed region / K) and ``roofline`` (the same K launches between
+two HIP events on their stream). ``--dump-outputs DIR`` writes what the last timed step returned to
+its caller as ``DIR/<name>.npy`` (float64; the inputs are seeded, so two builds compare output for
+output). Everything that takes runs of its own is behind ``--full``: at N=1 ``cpu_baseline`` (the
+reference's own circe crc32c() compiled from the reference tree into oracle/_ref, timed on the host
+cores) and the parity check of every digest against it, the Zipf size buckets, each host route on
+its own; at N>1 every rank's solo rate and its shard's check against the C oracle.
 """
 from __future__ import annotations
 
@@ -167,6 +172,52 @@ def host_cores() -> tuple[int, str]:
     return max(1, cores), why
 
 
+DUMP_LIMIT = 64_000_000  # bytes: everything one run writes under --dump-outputs, all ranks together
+DUMP_SEED = 44
+
+
+def dump_outputs(dirpath: str, arrays: dict, rank: int = 0, world: int = 1) -> dict:
+    """--dump-outputs: each named array as DIR/<name>.npy in float64 (u32 digests and i32 statuses are
+    exact there), `<name>_rank<r>.npy` when several ranks write. An array over its share of DUMP_LIMIT
+    is cut to a fixed sample: sorted indices drawn without replacement from default_rng(DUMP_SEED),
+    themselves written as DIR/<name>_index.npy. Returns {file name: element count}."""
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    share = DUMP_LIMIT // (world * max(1, len(arrays)))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.size * 8 > share:  # values + their indices, 8 B each
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(dirpath, f"{name}_index{suffix}.npy"), idx.astype(np.float64))
+            written[f"{name}_index{suffix}.npy"] = int(idx.size)
+            a = a[idx]
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a.astype(np.float64))
+        written[f"{name}{suffix}.npy"] = int(a.size)
+    return written
+
+
+# label, cores, cores_from of a CPU leg that had to fall back to the C oracle
+ORACLE_LEG = ("the plain-C table-driven oracle (oracle/crc_oracle.c) on one thread, because the reference's "
+              "crc32c() is not built here: a parity check, not the reference's rate", 1, "the C oracle is single-threaded")
+
+
+def _oracle_crc32c_run(host: np.ndarray, offs: np.ndarray, lens: np.ndarray, out: np.ndarray):
+    """run(threads, reps) -> seconds, like the timed entry points of oracle/_ref and oracle/cpu_baseline.c,
+    over the C oracle's CRC32C batch (threads is ignored: it has one)."""
+    import oracle
+    lib = oracle.lib()
+    args = (oracle.CRC32C, host.ctypes.data_as(oracle._u8p), offs.ctypes.data_as(oracle._u64p),
+            lens.ctypes.data_as(oracle._u32p), offs.size, None, 0, out.ctypes.data_as(oracle._u32p))
+
+    def run(thr, reps, _alive=(host, offs, lens, out)):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            lib.oracle_batch(*args)
+        return time.perf_counter() - t0
+    return run
+
+
 def cpu_baseline(host_sample: np.ndarray, entry_len: int, algo: int = 0, budget_s: float = 8.0):
     """Reference circe crc32c() (oracle/_ref) over the sample on one core and on every host core
     (all physical host cores)."""
@@ -181,6 +232,10 @@ def cpu_baseline(host_sample: np.ndarray, entry_len: int, algo: int = 0, budget_
         kind = "reference"
         run = lambda thr, reps: ref.ref_crc32c_uniform_timed(u8p, entry_len, entry_len, n, thr, reps, o32)
         label = "circe crc32c() (crc32c_sse42.cpp, chunk ladder {4096,512,64}) compiled from /root/reference"
+    elif algo == 0:  # CRC32C where oracle/_ref was never built: the C oracle checks the digests
+        kind, label, cores, cores_why = ("oracle",) + ORACLE_LEG
+        offs = np.arange(n, dtype=np.uint64) * np.uint64(entry_len)
+        run = _oracle_crc32c_run(host_sample, offs, np.full(n, entry_len, dtype=np.uint32), out)
     else:  # CRC-32: the JDK intrinsic's PCLMULQDQ folding, restated (oracle/cpu_baseline.c)
         kind = "port"
         lib = oracle.lib()
@@ -194,8 +249,11 @@ def cpu_baseline(host_sample: np.ndarray, entry_len: int, algo: int = 0, budget_
                  "oracle/cpu_baseline.c")
     t1 = run(1, 1)  # calibrate on one core
     one_core = host_sample.size / t1 / GIB
-    reps = max(1, int(budget_s / max(1e-6, t1 / cores)))
-    t = run(cores, reps)
+    if kind == "oracle":  # 0.3 GiB/s: its calibration pass is its measurement
+        reps, t = 1, t1
+    else:
+        reps = max(1, int(budget_s / max(1e-6, t1 / cores)))
+        t = run(cores, reps)
     value = host_sample.size * reps / t / GIB
     return {"value": round(value, 3), "unit": "GiB/s", "cores": cores, "kind": kind,
             "single_core_value": round(one_core, 3), "cpu_model": _cpu_model(), "cores_from": cores_why,
@@ -222,6 +280,9 @@ def cpu_baseline_indexed(host: np.ndarray, offs: np.ndarray, lens: np.ndarray, a
         def run(thr, reps):
             return ref.ref_crc32c_batch_timed(u8p, o64.ctypes.data_as(oracle._u64p), l32.ctypes.data_as(oracle._u32p),
                                               n, thr, reps, out.ctypes.data_as(oracle._u32p))
+    elif algo == 0:  # CRC32C where oracle/_ref was never built: the C oracle checks the digests
+        kind, label, cores, cores_why = ("oracle",) + ORACLE_LEG
+        run = _oracle_crc32c_run(host, o64, l32, out)
     else:
         kind = "port"
         label = ("PCLMULQDQ 4x128-bit folding, the arithmetic of java.util.zip.CRC32's HotSpot intrinsic "
@@ -235,8 +296,11 @@ def cpu_baseline_indexed(host: np.ndarray, offs: np.ndarray, lens: np.ndarray, a
                                                        out.ctypes.data_as(oracle._u32p))
     nbytes = int(l32.sum())
     t1 = run(1, 1)
-    reps = max(1, int(budget_s / max(1e-6, t1 / cores)))
-    t = run(cores, reps)
+    if kind == "oracle":  # 0.3 GiB/s: its calibration pass is its measurement
+        reps, t = 1, t1
+    else:
+        reps = max(1, int(budget_s / max(1e-6, t1 / cores)))
+        t = run(cores, reps)
     return {"value": round(nbytes * reps / t / GIB, 3), "unit": "GiB/s", "cores": cores, "kind": kind,
             "single_core_value": round(nbytes / t1 / GIB, 3), "cpu_model": _cpu_model(), "cores_from": cores_why,
             "sample": f"the first {n} entries of the same Zipf index ({nbytes / GIB:.3f} GiB), {reps} passes over "
@@ -340,8 +404,10 @@ def host_bench(args, ck, torch, rank) -> None:
         return (time.perf_counter() - t0) / args.steps, got
     auto = _route_name(ck, ck.get_host_batch_route())
     el, out = timed()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"digests": out.view(np.uint32)})
     routes = {}
-    for route in (ck.HOST_ROUTE_CPU, ck.HOST_ROUTE_GPU):
+    for route in (ck.HOST_ROUTE_CPU, ck.HOST_ROUTE_GPU) if args.full else ():
         with ck.host_batch_route(route):
             tr, got = timed()
         assert (got == out).all(), "routes disagree"
@@ -355,7 +421,7 @@ def host_bench(args, ck, torch, rank) -> None:
                                   f"{'pageable' if args.pageable else 'pinned'} source; GPU route: 64 MiB "
                                   f"double-buffered segments incl. PCIe H2D/D2H; CPU route: host threads"},
            "digest_of_digests": int(np.bitwise_xor.reduce(out))}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cb, want = cpu_baseline(host, entry_len, 0, budget_s=3.0)
         res["cpu_baseline"] = cb
         res["parity_check"] = {"entries": n, "match": bool((want == out).all())}
@@ -423,8 +489,11 @@ def digest_host_bench(args, ck, torch, rank, algo) -> None:
     ok = bool((status == 0).all()) and first_bad.value == n
     t_pack = timed(package)
     ok = ok and bool((digests == first_digests).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verify_status": status, "verify_first_bad": [first_bad.value],
+                                         "package_digests": digests, "package_frames": hdrs})
     routes = {}
-    for route in (ck.HOST_ROUTE_CPU, ck.HOST_ROUTE_GPU):
+    for route in (ck.HOST_ROUTE_CPU, ck.HOST_ROUTE_GPU) if args.full else ():
         with ck.host_batch_route(route):
             tv = timed(verify)
             rok = bool((status == 0).all()) and first_bad.value == n
@@ -445,7 +514,11 @@ def digest_host_bench(args, ck, torch, rank, algo) -> None:
            "all_verified": ok, "entries_per_s": round(n / t_verify, 0),
            "package": {"GiB_s_payload": round(n * plen / t_pack / GIB, 2), "ms": round(t_pack * 1e3, 3),
                        "entries_per_s": round(n / t_pack, 0)}}
-    if rank == 0 and not args.no_cpu_baseline:
+    want_cpu = rank == 0 and args.full and not args.no_cpu_baseline
+    if want_cpu and algo == ck.CRC32C:
+        import oracle
+        want_cpu = oracle.ref() is not None  # CRC32C's CPU leg is the reference's own crc32c() (oracle/_ref)
+    if want_cpu:
         cb, st = _host_reference_verify(frame_ptrs, frame_lens, n, dm.ledgerId, algo)
         res["cpu_baseline"] = cb
         res["parity_check"] = {"entries": n, "match": bool((st == status).all())}
@@ -499,6 +572,13 @@ def digest_bench(args, ck, torch, rank, dev, stream, algo) -> None:
     ok = bool((status == 0).all().item()) and int(first_bad.item()) == n
     if args.digest_op in ("both", "package"):
         t_pack = timed(lambda: dm.package_batch(ids, lacs, len_field, framed, pay_off, pay_len, stream=stream))
+    if args.dump_outputs:  # verify's and package's returns; both calls are deterministic on these inputs
+        frames, digests = dm.package_batch(ids, lacs, len_field, framed, pay_off, pay_len, stream=stream)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"verify_status": status.cpu().numpy(),
+                                         "verify_first_bad": first_bad.cpu().numpy(),
+                                         "package_digests": digests.cpu().numpy().view(np.uint32),
+                                         "package_frames": frames.cpu().numpy()})
     # algorithmic bytes: verify reads every framed byte + 12 B of index, writes a 4 B status;
     # package reads the payload + 24 B of ids/LAC/length + 12 B of index, writes header+digest + 4 B
     v_bytes = n * (L + 12 + 4)
@@ -546,6 +626,12 @@ def main() -> None:
     ap.add_argument("--algo", default="crc32c", choices=["crc32c", "crc32"])
     ap.add_argument("--entries", type=int, default=0, help="entries per GPU (default by config)")
     ap.add_argument("--lanes", type=int, default=0, help="force lanes per entry group (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the CPU baseline and the parity check against it, "
+                         "the Zipf size buckets, each host route alone; at N > 1 every rank's solo rate and its "
+                         "shard's check against the oracle (--no-cpu-baseline, --no-check, --no-buckets drop one each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--zipf-align", type=int, default=1, help="diagnostic: align Zipf entries")
@@ -706,7 +792,7 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
     torch.cuda.synchronize()
 
     solo_kernel_s = None
-    if world > 1:  # each rank alone on the node, in turn: the same-run 1-GPU rate per rank
+    if world > 1 and args.full:  # each rank alone on the node, in turn: the same-run 1-GPU rate per rank
         for r in range(world):
             dist.barrier()
             if r == rank:
@@ -740,10 +826,12 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
 
     coll_dev = dev if args.dist_backend == "nccl" else None
     elapsed_max = max_over_ranks(elapsed, coll_dev)
-    # N > 1: every rank checks a sample of its own shard against the C oracle after the timed region
-    # (N = 1 checks the whole batch against the reference in the cpu_baseline leg below)
+    if args.dump_outputs:  # `out` is what the last timed step handed back
+        dump_outputs(args.dump_outputs, {"digests": out.cpu().numpy().view(np.uint32)}, rank, world)
+    # --full, N > 1: every rank checks a sample of its own shard against the C oracle after the timed
+    # region (N = 1 checks the whole batch against the reference in the cpu_baseline leg below)
     shard_check = None
-    if world > 1 and not args.no_check:
+    if world > 1 and args.full and not args.no_check:
         shard_check = shard_parity(ck, torch, algo, args.config, base, out, n,
                                    entry_len if args.config in ("uniform4k", "shard8m") else 0,
                                    None if args.config in ("uniform4k", "shard8m") else (offs, lens))
@@ -756,6 +844,7 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
     total_payload = (split["bytes_total"] if split else payload_bytes * world) * args.steps
     value = total_payload / elapsed_max / GIB
     achieved_gbs = algo_bytes / avg_kernel_s / 1e9
+    solo_measured = world == 1 or args.full
     result = {
         "metric": metric_for(args.config, args.algo),
         "value": round(value, 2),
@@ -777,10 +866,11 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
                      "frac": round(achieved_gbs / HBM_PEAK_GBS, 4), "traffic": _pmc_traffic(args.config),
                      "kernel": kernel_name, "avg_kernel_ms": round(avg_kernel_s * 1e3, 4),
                      "algorithmic_bytes_per_launch": algo_bytes},
-        # per GPU: its own wall rate over the timed region, its kernel time, and (N > 1) its rate when
-        # it ran alone on the node in this same run; efficiency = (aggregate / N) / mean solo rate
-        "per_gpu": [{"rank": r, "GiB_s": round(payload_bytes * args.steps / e / GIB, 2),
-                     "kernel_ms": round(k * 1e3, 4), "solo_GiB_s": round(payload_bytes / so / GIB, 2), **idents[r],
+        # per GPU: its own wall rate over the timed region, its kernel time, and (--full; at N = 1 the
+        # timed region's own rate) its rate when it ran alone on the node in this same run; efficiency =
+        # (aggregate / N) / mean solo rate
+        "per_gpu": [{"rank": r, "GiB_s": round(payload_bytes * args.steps / e / GIB, 2), "kernel_ms": round(k * 1e3, 4),
+                     **({"solo_GiB_s": round(payload_bytes / so / GIB, 2)} if solo_measured else {}), **idents[r],
                      **({"parity_check": {"entries": int(pe), "match": bool(pm)}} if shard_check else {})}
                     for r, (e, k, so, pe, pm) in enumerate(per_rank)],
         "per_gpu_GiB_s": round(value / world, 2),
@@ -789,7 +879,7 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
         result["per_launch_ms"] = [round(a.elapsed_time(b), 4) for a, b in trace]
         result["trace_note"] = (f"HIP events around every launch: launches 0..{args.warmup - 1} warm-up, "
                                 f"{args.warmup}..{args.warmup + args.steps - 1} the timed region")
-    if world > 1:
+    if world > 1 and solo_measured:
         solo_mean = float(np.mean([payload_bytes / so / GIB for _, _, so, _, _ in per_rank]))
         result["efficiency_vs_solo"] = round(value / world / solo_mean, 4)
     if shard_check:
@@ -800,9 +890,10 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
             if rank == 0:
                 print(json.dumps(result), flush=True)
             raise SystemExit("PARITY FAILURE: a rank's GPU digests differ from the oracle's")
-    if args.config in ("zipf", "zipf_split") and world == 1 and not args.no_buckets:
+    want_cpu = args.full and not args.no_cpu_baseline  # the CPU baseline and the parity check against it
+    if args.full and args.config in ("zipf", "zipf_split") and world == 1 and not args.no_buckets:
         result["buckets"] = bucket_rates(ck, torch, algo, base, offs, lens, stream, max(3, args.steps))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in ("zipf", "zipf_split"):
+    if rank == 0 and world == 1 and want_cpu and args.config in ("zipf", "zipf_split"):
         m = n  # the whole packed batch (6.3 GiB for config 3): well past any cache
         span = int(offs[m - 1] + lens[m - 1])
         host = np.ascontiguousarray(base[:span].cpu().numpy())
@@ -812,7 +903,7 @@ def run_rank(args, ck, torch, dist, world: int, rank: int, dev) -> None:
         if not result["parity_check"]["match"]:
             print(json.dumps(result), flush=True)
             raise SystemExit("PARITY FAILURE: GPU digests differ from the CPU baseline's")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in ("uniform4k", "shard8m"):
+    if rank == 0 and world == 1 and want_cpu and args.config in ("uniform4k", "shard8m"):
         # cpu_baseline leg: the reference timed on the host cores over a bounded sample; its
         # digests for that sample double as a parity spot check of the GPU output.
         m = min(n, 1 << 20)  # config 1's full 1M x 4 KiB (4 GiB)

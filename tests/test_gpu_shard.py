@@ -125,7 +125,7 @@ def test_bench_self_launches_ranks(gpu):
     """bench.py --gpus 2 outside torch.distributed.run starts its own two ranks (gloo here, both on
     this GPU) and rank 0 reports n_gpus 2 with per-GPU numbers."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--entries",
-           "65536", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+           "65536", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -142,7 +142,7 @@ def test_bench_two_ranks_default_is_config4_shard(gpu):
     this one card (2 x 32 GiB of HBM); the driver's N = 2/4/8 runs use nccl (= RCCL) for the same
     three timing collectives."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "5",
-           "--warmup", "2", "--no-cpu-baseline"]
+           "--warmup", "2", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -174,7 +174,8 @@ def test_bench_zipf_split_by_bytes_two_ranks(gpu):
     over the slowest rank's time. Each rank checks 65 536 of its entries against the C oracle."""
     n = 1 << 18
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--config",
-           "zipf_split", "--entries", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "zipf_split", "--entries", str(n), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -12,8 +12,12 @@ reference it plugs into, without a JDK (none exists in this image, SURVEY.md §8
   NativeUtils.java:54-116, the provider chain's capability flags, DigestManager's ledgerId and
   verifyDigestAndReturnData, ByteBufList's accessors).
 
-Skipped when /root/reference is absent (the GPU box)."""
+The import and package checks resolve against tests/golden/reference_java_classes.json, the names
+of the reference's class files (tests/golden/make_java_index.py), so they run everywhere; where the
+reference tree is present the list is checked against it. The checks that read the reference's
+source text are skipped where the tree is absent."""
 import glob
+import json
 import os
 import re
 
@@ -23,7 +27,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 JAVA = os.path.join(ROOT, "native", "java")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+
+with open(os.path.join(ROOT, "tests", "golden", "reference_java_classes.json")) as _f:
+    REF_CLASSES = {tree: set(names) for tree, names in json.load(_f).items()}
 
 # java.lang types the sources use without an import
 JAVA_LANG = {"String", "Object", "Throwable", "Exception", "RuntimeException", "IllegalArgumentException",
@@ -60,16 +67,38 @@ def _ref_class_file(fqcn):
     return None
 
 
+def _resolves(fqcn):
+    """fqcn (or its enclosing class) names a class file of the reference's main sources, by the
+    committed list of their names, or of native/java."""
+    parts = fqcn.split(".")
+    for k in range(len(parts), 1, -1):  # a.b.C.D -> a/b/C/D.java, then a/b/C.java (nested)
+        rel = "/".join(parts[:k]) + ".java"
+        if rel in REF_CLASSES["main"] or os.path.exists(os.path.join(JAVA, *parts[:k]) + ".java"):
+            return True
+        if not parts[k - 1][:1].isupper():
+            break
+    return False
+
+
 def _package_has(pkg, name, tests=False):
     """A class of pkg in the reference's main sources or native/java; with tests, also the reference's
     test sources (the JUnit tests under native/java-test sit beside them)."""
-    rel = os.path.join(*pkg.split("."), name + ".java")
+    rel = "/".join(pkg.split(".") + [name + ".java"])
     trees = ("main", "test") if tests else ("main",)
-    return any(glob.glob(os.path.join(REF, "**", "src", t, "java", rel), recursive=True) for t in trees) or \
-        os.path.exists(os.path.join(JAVA, rel))
+    return any(rel in REF_CLASSES[t] for t in trees) or os.path.exists(os.path.join(JAVA, *rel.split("/")))
 
 
-@pytest.mark.parametrize("path", _sources() if os.path.isdir(REF) else [], ids=os.path.basename)
+@needs_reference
+def test_committed_class_list_is_the_reference_trees():
+    """The list the checks below resolve against names exactly the class files of the reference."""
+    for tree in ("main", "test"):
+        marker = os.path.join("src", tree, "java") + os.sep
+        found = {p.split(marker, 1)[1].replace(os.sep, "/")
+                 for p in glob.glob(os.path.join(REF, "**", "src", tree, "java", "**", "*.java"), recursive=True)}
+        assert found == REF_CLASSES[tree], tree
+
+
+@pytest.mark.parametrize("path", _sources(), ids=os.path.basename)
 def test_imports_resolve(path):
     src = open(path).read()
     pkg = _package(src)
@@ -80,7 +109,7 @@ def test_imports_resolve(path):
             imported.add(name.rsplit(".", 1)[1])
             continue
         fq = name.rsplit(".", 1)[0] if static else name
-        assert _ref_class_file(fq), f"{os.path.basename(path)}: import {name} resolves to no class"
+        assert _resolves(fq), f"{os.path.basename(path)}: import {name} resolves to no class"
         imported.add(name.rsplit(".", 1)[1])
     body = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
     used = set(re.findall(r"\b(?:new|instanceof|implements|extends)\s+([A-Z]\w*)", body))
@@ -91,6 +120,7 @@ def test_imports_resolve(path):
             f"{os.path.basename(path)}: {name} is not a class of {pkg}"
 
 
+@needs_reference
 def test_gpu_int_hash_implements_every_int_hash_method():
     iface = open(_ref_class_file("com.scurrilous.circe.checksum.IntHash")).read()
     methods = re.findall(r"^\s+(\w+)\s+(\w+)\(([^)]*)\);", iface, re.M)
@@ -153,6 +183,7 @@ MEMBERS = [
 ]
 
 
+@needs_reference
 @pytest.mark.parametrize("cls,decl", MEMBERS, ids=[f"{c.rsplit('.', 1)[1]}:{i}" for i, (c, _) in enumerate(MEMBERS)])
 def test_reference_members_exist(cls, decl):
     path = _ref_class_file(cls)
@@ -224,6 +255,7 @@ def verifier_problems(src):
     return problems
 
 
+@needs_reference
 def test_batch_verifier_leaves_buffers_as_the_reference():
     assert verifier_problems(open(VERIFIER).read()) == []
     # the reference member the loop relies on (package-private, same package)
@@ -247,6 +279,7 @@ def test_batch_verifier_check_catches(mutation):
     assert verifier_problems(src.replace(old, new)) != []
 
 
+@needs_reference
 def test_batch_packager_builds_the_reference_objects():
     """GpuBatchPackager's V2 buffer is built with the statements of computeDigestAndPackageForSendingV2
     (DigestManager.java:126-167) — the same small-entry test, header sizes, allocation, the three

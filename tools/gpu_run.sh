@@ -6,11 +6,12 @@
 # Steps:
 #   tests            pytest -m gpu (the driver's suite)        tests:EXPR  only tests matching -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   driver           bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command)
+#   driver           bench.py --gpus 1 --steps 20 --warmup 5 (the driver's command: the timed steps only)
+#   driver_full      the driver's command with --full (adds the CPU baseline and the parity check against it)
 #   trace            the driver's command with --trace-launches (HIP events around every launch)
 #   bench100         bench.py --steps 100 --warmup 50
-#   zipf | zipf32    bench.py --config zipf [--algo crc32]
-#   verify | shard8m bench.py --config verify4k | shard8m
+#   zipf | zipf32    bench.py --config zipf [--algo crc32] --full (size buckets, CPU baseline, parity check)
+#   verify | shard8m bench.py --config verify4k | shard8m --full
 #   stats_uniform | stats_zipf   rocprofv3 --kernel-trace --stats of the driver's command / zipf
 #   pmc_uniform | pmc_zipf       FETCH_SIZE and WRITE_SIZE passes (separate) + tools/pmc_summary.py
 #   pmc_verify | pmc_package     the same for bench.py --config verify4k --digest-op verify | package
@@ -36,12 +37,13 @@ for step in "$@"; do
     tests:*) run pytest_gpu_sel 900 python3 -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests -k "${step#tests:}" ;;
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
     driver) run bench_driver 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    driver_full) run bench_driver_full 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
     trace) run bench_driver_trace 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --trace-launches ;;
     bench100) run bench_100 200 python3 bench.py --steps 100 --warmup 50 --no-cpu-baseline ;;
-    zipf) run bench_zipf 300 python3 bench.py --config zipf ;;
-    zipf32) run bench_zipf_crc32 300 python3 bench.py --config zipf --algo crc32 ;;
+    zipf) run bench_zipf 300 python3 bench.py --config zipf --full ;;
+    zipf32) run bench_zipf_crc32 300 python3 bench.py --config zipf --algo crc32 --full ;;
     verify) run bench_verify4k 300 python3 bench.py --config verify4k ;;
-    shard8m) run bench_shard8m 300 python3 bench.py --config shard8m ;;
+    shard8m) run bench_shard8m 300 python3 bench.py --config shard8m --full ;;
     stats_uniform) (cd /tmp && export TMPDIR=/tmp && run stats_uniform 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_u -o uniform4k -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline) || exit 1 ;;
     stats_zipf) (cd /tmp && export TMPDIR=/tmp && run stats_zipf 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_z -o zipf -- python3 $R/bench.py --config zipf --no-buckets --no-cpu-baseline) || exit 1 ;;
     pmc_uniform|pmc_zipf)
