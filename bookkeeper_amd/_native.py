@@ -27,6 +27,8 @@ VERIFY_DIGEST_MISMATCH = 2
 VERIFY_LEDGER_MISMATCH = 3
 VERIFY_ENTRY_MISMATCH = 4
 
+REFRAME_TRUSTED = 1  # BKD_REFRAME_TRUSTED
+
 HEADER_PATH = os.path.join(ROOT, "include", "bkdigest.h")
 
 
@@ -73,6 +75,9 @@ PROTOTYPES = {
     "bkd_digest_package_batch_host": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "bkd_digest_package_batch": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "bkd_digest_verify_batch": (_int, [_int, _i64, _i64, _int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_digest_reframe_batch": (_int, [_int, _i64, _i64, _int, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                        _vp, _vp, _vp]),
+    "bkd_digest_reframe_batch_host": (_int, [_int, _i64, _i64, _int, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "bkd_entrylog_index": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_verify": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),

@@ -169,6 +169,7 @@ struct DeviceState {
     int cus = 0;
     uint32_t* tables[2][kNumLaneChoices] = {};  // [algo][lane choice] compact operator images
     uint32_t* xinv[2] = {};       // [algo] x^(-8k), k = 0..127: removes the plan's zero padding
+    uint32_t* xp8[2] = {};        // [algo] word 256 k + b = x^(8 b 256^k), k = 0..3 (reframe_frame_kernel)
     std::shared_mutex maps_mu;    // guards xtab and scratch
     std::map<uint64_t, uint32_t*> xtab;  // (algo, CH) -> x^(8*CH) operator for the plan's combine
     std::map<hipStream_t, std::unique_ptr<StreamScratch>> scratch;
@@ -273,6 +274,11 @@ int init_device_locked(int dev) {
         for (uint32_t k = 0; k < 128; ++k) inv[k] = bkd::gf2::xpow_neg8(algo, k);
         BKD_HIP(hipMalloc(&ds.xinv[algo], sizeof(inv)));
         BKD_HIP(hipMemcpy(ds.xinv[algo], inv, sizeof(inv), hipMemcpyHostToDevice));
+        std::vector<uint32_t> xp(1024);
+        for (uint32_t k = 0; k < 4u; ++k)
+            for (uint64_t b = 0; b < 256u; ++b) xp[256u * k + b] = bkd::gf2::xpow(algo, (8ull * b) << (8u * k));
+        BKD_HIP(hipMalloc(&ds.xp8[algo], xp.size() * sizeof(uint32_t)));
+        BKD_HIP(hipMemcpy(ds.xp8[algo], xp.data(), xp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     BKD_HIP(hipSetDevice(prev));
     ds.ready.store(true, std::memory_order_release);
@@ -644,13 +650,26 @@ struct HostStage {
         fb_ready = true;
         return BKD_OK;
     }
+    // reframe: the new LACs in (8 B per entry); its digests come back through d_seed / h_seed
+    bool lac_ready = false;
+    int64_t* h_lac[2] = {};
+    int64_t* d_lac[2] = {};
+    int init_reframe() {
+        if (lac_ready) return BKD_OK;
+        for (int s = 0; s < 2; ++s) {
+            if (!h_lac[s]) BKD_HIP(hipHostMalloc((void**)&h_lac[s], kSegEntries * 8, hipHostMallocDefault));
+            if (!d_lac[s]) BKD_HIP(hipMalloc((void**)&d_lac[s], kSegEntries * 8));
+        }
+        lac_ready = true;
+        return BKD_OK;
+    }
     ~HostStage() {  // (bkd_host_release: idle sets only, so no work of theirs is queued)
         for (int s = 0; s < 2; ++s) {
             for (void* h : {(void*)h_pin[s], (void*)h_off[s], (void*)h_len[s], (void*)h_seed[s], (void*)h_res[s],
-                            (void*)h_aux[s], (void*)h_frm[s], (void*)h_fb[s]})
+                            (void*)h_aux[s], (void*)h_frm[s], (void*)h_fb[s], (void*)h_lac[s]})
                 if (h) (void)hipHostFree(h);
             for (void* d : {(void*)d_buf[s], (void*)d_off[s], (void*)d_len[s], (void*)d_seed[s], (void*)d_res[s],
-                            (void*)d_aux[s], (void*)d_frm[s], (void*)d_fb[s]})
+                            (void*)d_aux[s], (void*)d_frm[s], (void*)d_fb[s], (void*)d_lac[s]})
                 if (d) (void)hipFree(d);
             if (st[s]) (void)hipStreamDestroy(st[s]);
             if (done[s]) (void)hipEventDestroy(done[s]);
@@ -1069,6 +1088,46 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
                        (unsigned long long*)d_first_bad, vflag, vepoch);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
+    return BKD_OK;
+}
+
+// Reframe (bkd_digest_reframe_batch): the verify sequence above (unless trusted), then one thread per
+// frame writes the new LAC and old digest ^ R(LAC difference) * x^(8 * payload length) for the frames
+// whose status is OK (reframe_frame_kernel) — no second pass over the payloads. Trusted: the kernel
+// takes the status from each header itself and no payload byte is read at all.
+int reframe_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, int64_t first_entry_id,
+                   int id_checks, bool trusted, void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                   const uint32_t* d_lengths, uint64_t n, const int64_t* d_new_lacs, void* d_out_frames,
+                   uint64_t frame_stride, uint32_t* d_digests, int32_t* d_status, uint64_t* d_first_bad) {
+    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    if (n == 0) {
+        BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
+        return BKD_OK;
+    }
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // verify and reframe enqueued as one sequence
+    if (!trusted) {
+        const int rc = verify_framed(ds, st, algo, ledger_id, first_entry_id, id_checks, d_framed, framed_size,
+                                     d_offsets, d_lengths, n, d_status, d_first_bad);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(bkd::reframe_first_bad_kernel, dim3(1), dim3(1), 0, st, d_first_bad, n);
+        BKD_HIP(hipGetLastError());
+    }
+    const uint32_t* x32tab = ds.tables[algo][lane_index(4)] + 1024;  // x^32 operator, 4 x 256
+    const uint64_t ntiles = (n + bkd::kReframeBlock - 1) / bkd::kReframeBlock;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(ntiles, 8u * (uint64_t)ds.cus);
+    if (trusted)
+        hipLaunchKernelGGL(bkd::reframe_frame_kernel<true>, dim3(blocks), dim3(bkd::kReframeBlock), 0, st, x32tab,
+                           ds.xp8[algo], bkd::gf2::poly(algo), (uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
+                           mac, d_new_lacs, ledger_id, first_entry_id, id_checks, (uint8_t*)d_out_frames, frame_stride,
+                           d_digests, d_status, (unsigned long long*)d_first_bad);
+    else
+        hipLaunchKernelGGL(bkd::reframe_frame_kernel<false>, dim3(blocks), dim3(bkd::kReframeBlock), 0, st, x32tab,
+                           ds.xp8[algo], bkd::gf2::poly(algo), (uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
+                           mac, d_new_lacs, ledger_id, first_entry_id, id_checks, (uint8_t*)d_out_frames, frame_stride,
+                           d_digests, d_status, (unsigned long long*)d_first_bad);
+    BKD_HIP(hipGetLastError());
     return BKD_OK;
 }
 
@@ -1794,6 +1853,96 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
         return BKD_OK;
     };
     return host_segments(hs, h_lengths, n, max_entries, seg, drain);
+}
+
+int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check, uint32_t flags,
+                             void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                             const uint32_t* d_lengths, uint64_t n, const int64_t* d_new_lacs, void* d_out_frames,
+                             uint64_t frame_stride, uint32_t* d_digests, int32_t* d_status, uint64_t* d_first_bad,
+                             void* stream) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (flags & ~BKD_REFRAME_TRUSTED) return fail(BKD_ERR_INVALID_ARG, "unknown reframe flags");
+    if (!d_first_bad) return fail(BKD_ERR_INVALID_ARG, "null first_bad");
+    if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
+    if (n && !d_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
+    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    if (n && d_out_frames) {
+        if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+        const uint64_t fr0 = (uint64_t)(uintptr_t)d_out_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
+        const uint64_t in0 = (uint64_t)(uintptr_t)d_framed, in1 = in0 + framed_size;
+        if (fr0 < in1 && in0 < fr1) return fail(BKD_ERR_INVALID_ARG, "out_frames overlaps the framed buffer");
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    DeviceScope scope;
+    DeviceState* ds = nullptr;
+    int rc = enter(st, scope, &ds);
+    if (rc) return rc;
+    return reframe_framed(*ds, st, algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0,
+                          (flags & BKD_REFRAME_TRUSTED) != 0, d_framed, framed_size, d_offsets, d_lengths, n, d_new_lacs,
+                          d_out_frames, frame_stride, d_digests, d_status, d_first_bad);
+}
+
+int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check,
+                                  uint32_t flags, void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                                  const int64_t* h_new_lacs, uint32_t* h_digests, int32_t* h_status,
+                                  uint64_t* h_first_bad) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (flags & ~BKD_REFRAME_TRUSTED) return fail(BKD_ERR_INVALID_ARG, "unknown reframe flags");
+    if (!h_first_bad) return fail(BKD_ERR_INVALID_ARG, "null first_bad");
+    *h_first_bad = n;
+    if (n == 0) return BKD_OK;
+    if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (!h_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
+    const bool trusted = (flags & BKD_REFRAME_TRUSTED) != 0;
+    const int id_checks = skip_entry_check ? 1 : 0;
+    const int route = host_route(any_longer(h_lengths, n, HostStage::kSeg));
+    if (route < 0) return route;
+    if (route == 1) {
+        *h_first_bad = bkd::host::reframe_frames(algo, ledger_id, first_entry_id, id_checks, trusted,
+                                                 (uint8_t* const*)h_frames, h_lengths, n, h_new_lacs, h_digests,
+                                                 h_status);
+        return BKD_OK;
+    }
+    DeviceScope scope;
+    DeviceState* ds = nullptr;
+    int rc = enter(nullptr, scope, &ds);
+    if (rc) return rc;
+    StageLease lease((int)(ds - g_dev));
+    HostStage& hs = *lease;
+    if ((rc = hs.init()) || (rc = hs.init_verify()) || (rc = hs.init_reframe())) return rc;
+    // staged as verify; the device reframes its copy in place and only status and digests come back
+    // (d_seed / h_seed carry the digests), then the host threads write each OK frame's 12 bytes
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        gather_entries(h_frames + i0, h_lengths + i0, cnt, hs.h_pin[s], hs.h_off[s]);
+        memcpy(hs.h_lac[s], h_new_lacs + i0, cnt * 8);
+        const hipStream_t st = hs.st[s];
+        BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, st));
+        BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, st));
+        BKD_HIP(hipMemcpyAsync(hs.d_len[s], h_lengths + i0, cnt * 4, hipMemcpyHostToDevice, st));
+        BKD_HIP(hipMemcpyAsync(hs.d_lac[s], hs.h_lac[s], cnt * 8, hipMemcpyHostToDevice, st));
+        uint64_t* d_fb = hs.d_fb[s];
+        int r = reframe_framed(*ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, trusted, hs.d_buf[s],
+                               bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_lac[s], nullptr, 0, hs.d_seed[s],
+                               reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        BKD_HIP(hipMemcpyAsync(hs.h_seed[s], hs.d_seed[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        BKD_HIP(hipMemcpyAsync(hs.h_fb[s], d_fb, 8, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
+        if (h_digests) memcpy(h_digests + i0, hs.h_seed[s], cnt * 4);
+        bkd::host::apply_reframe(algo, (uint8_t* const*)h_frames + i0, cnt, h_new_lacs + i0,
+                                 reinterpret_cast<const int32_t*>(hs.h_res[s]), hs.h_seed[s]);
+        const uint64_t fb = *hs.h_fb[s];
+        if (fb < cnt && i0 + fb < *h_first_bad) *h_first_bad = i0 + fb;
+        return BKD_OK;
+    };
+    return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
 }
 
 int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,

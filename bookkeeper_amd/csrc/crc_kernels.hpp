@@ -1726,6 +1726,18 @@ __global__ void fill_splitmix64_kernel(uint8_t* __restrict__ dst, uint64_t nbyte
     }
 }
 
+// a * b mod P, bitwise (no tables): 32 shift/xor steps, for the few products per entry that have
+// no operator table (x^(-8*pad), powers of X, a re-framed entry's x^(8*len)).
+__device__ __forceinline__ uint32_t gf_mul_bits(uint32_t a, uint32_t b, uint32_t poly) {
+    uint32_t prod = 0u, cur = b;
+#pragma unroll
+    for (int k = 31; k >= 0; --k) {
+        prod ^= ((a >> k) & 1u) ? cur : 0u;
+        cur = (cur >> 1) ^ ((cur & 1u) ? poly : 0u);
+    }
+    return prod;
+}
+
 // ---- DigestManager framing helpers (one thread per entry; 32-byte headers) ----
 
 // Package step 1: header [ledgerId, entryId, LAC, length] BE into the frame
@@ -1833,7 +1845,181 @@ __global__ void __launch_bounds__(256) package_frame_kernel(int64_t ledger_id, c
     put_frame_digest(f + 32, dg, mac);
 }
 
-// Verify step 1 (one thread per framed entry [32 B header][mac][payload], DigestManager.java:226-283):
+// ---- re-framing with a new LAC (bkd_digest_reframe_batch) ------------------------------------
+// LedgerFragmentReplicator frames an entry it has just read and verified again with the ledger's
+// current LAC ($BK/client/LedgerFragmentReplicator.java:436-442, 506-511): the same ledger id, entry
+// id, length field and payload. CRC is affine over GF(2), so for the header H -> H' (same length)
+//   crc(H' || P) = crc(H || P) ^ R(H ^ H') * x^(8 |P|)  (mod P),
+// R(D) the register after folding the 32-byte difference D from a zero register (the init and
+// final-xor terms cancel). D is non-zero in header bytes 16..23 only, so R(D) is four x^32 steps: the
+// two LAC dwords, then the length field's two zero dwords. crc(H || P) is the digest stored in a frame
+// that verified: no payload byte is read here.
+//
+// One thread per frame, a block's 256 frames per tile (grid stride over tiles: the tables are staged
+// once per block). x^(8 len) = the product of up to four table words xp8[k][byte k of len] =
+// x^(8 * byte * 256^k), one bitwise product per non-zero length byte (a 4 KiB payload: one).
+// TRUSTED: the status comes from the header alone here (verifyDigest's order, DigestManager.java:
+// 226-283, without the digest comparison) instead of from the verify sequence that ran before.
+constexpr int kReframeBlock = 256;
+
+// Bytes [0, 32 + mac) of a frame as little-endian dwords (the rest of w zero): 16-byte loads when the
+// frame is 16-byte aligned and at least 48 bytes, dword loads when 4-byte aligned, bytes otherwise
+// (verify_header_kernel's three cases).
+__device__ __forceinline__ void load_frame_head(const uint8_t* f, uint32_t l, uint32_t mac, uint32_t (&w)[10]) {
+    const int nw = (int)(32u + mac) / 4;
+    if ((((uintptr_t)f) & 15u) == 0 && l >= 48u) {
+        const u32x4 v0 = *reinterpret_cast<const u32x4*>(f), v1 = *reinterpret_cast<const u32x4*>(f + 16),
+                    v2 = *reinterpret_cast<const u32x4*>(f + 32);
+        w[0] = v0.x, w[1] = v0.y, w[2] = v0.z, w[3] = v0.w;
+        w[4] = v1.x, w[5] = v1.y, w[6] = v1.z, w[7] = v1.w;
+        w[8] = v2.x, w[9] = nw > 9 ? v2.y : 0u;
+    } else if ((((uintptr_t)f) & 3u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) w[k] = k < nw ? reinterpret_cast<const uint32_t*>(f)[k] : 0u;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {
+            uint32_t v = 0u;
+            if (k < nw)
+                for (int b = 3; b >= 0; --b) v = (v << 8) | f[4 * k + b];
+            w[k] = v;
+        }
+    }
+}
+
+template <bool TRUSTED>
+__global__ void __launch_bounds__(kReframeBlock) reframe_frame_kernel(
+    const uint32_t* __restrict__ x32tab, const uint32_t* __restrict__ xp8tab, uint32_t poly, uint8_t* framed,
+    uint64_t size, const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac,
+    const int64_t* __restrict__ new_lacs, int64_t ledger_id, int64_t first_entry_id, int id_checks,
+    uint8_t* out_frames, uint64_t frame_stride, uint32_t* __restrict__ digests, int32_t* status,
+    unsigned long long* first_bad) {
+    __shared__ uint32_t W[1024];   // x^32 operator, 4 x 256
+    __shared__ uint32_t XP[1024];  // XP[256 k + b] = x^(8 b 256^k)
+    __shared__ uint32_t fr[kReframeBlock * 10];
+    __shared__ uint32_t okf[kReframeBlock];
+    for (int k = threadIdx.x; k < 1024; k += kReframeBlock) {
+        W[k] = x32tab[k];
+        XP[k] = xp8tab[k];
+    }
+    __syncthreads();
+    // packed out-frames (stride 32 + mac) on a 4-byte boundary: the tile's frames are built in LDS and
+    // stored as consecutive dwords (as package_frame_kernel), the dwords of frames that are not OK left out
+    const bool packed = out_frames && frame_stride == 32u + mac && (((uintptr_t)out_frames) & 3u) == 0;
+    const uint32_t fw = (32u + mac) / 4u;  // dwords per frame
+    const uint64_t ntiles = (n + kReframeBlock - 1) / kReframeBlock;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t i0 = tile * kReframeBlock;
+        const uint64_t i = i0 + threadIdx.x;
+        bool ok = false;
+        uint32_t w[10];
+        uint32_t digest = 0u;
+        if (i < n) {
+            const uint64_t o = offsets[i];
+            const uint32_t l = lengths[i];
+            // (checked in both modes: no status can send a read or a store outside the buffer)
+            const bool in_range = !(o > size || (uint64_t)l > size - o || l < 32u + mac);
+            int32_t st = 1;
+            if constexpr (TRUSTED) ok = in_range;
+            else ok = in_range && status[i] == 0;
+            uint8_t* f = framed + o;
+            if (ok) {
+                load_frame_head(f, l, mac, w);
+                if constexpr (TRUSTED) {
+                    const int64_t lid = (int64_t)(((uint64_t)__builtin_bswap32(w[0]) << 32) | __builtin_bswap32(w[1]));
+                    const int64_t eid = (int64_t)(((uint64_t)__builtin_bswap32(w[2]) << 32) | __builtin_bswap32(w[3]));
+                    if (mac == 8u && w[8] != 0u) st = 2;
+                    else if (id_checks < 2 && lid != ledger_id) st = 3;
+                    else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) st = 4;
+                    else st = 0;
+                    ok = st == 0;
+                }
+            }
+            if constexpr (TRUSTED) {
+                status[i] = st;
+                if (st != 0) atomicMin(first_bad, (unsigned long long)i);
+            }
+            if (ok) {
+                const uint64_t lac = (uint64_t)new_lacs[i];
+                const uint32_t n4 = __builtin_bswap32((uint32_t)(lac >> 32)), n5 = __builtin_bswap32((uint32_t)lac);
+                // R(D): the LAC difference's two dwords, then the length field's two zero dwords
+                uint32_t reg = 0u;
+                const uint32_t dw[4] = {w[4] ^ n4, w[5] ^ n5, 0u, 0u};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t r = reg ^ dw[k];
+                    reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
+                }
+                // * x^(8 payload_len); equal LACs (reg == 0) need no product
+                const uint32_t plen = l - 32u - mac;
+                if (reg != 0u) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t b = (plen >> (8 * k)) & 0xffu;
+                        if (b) reg = gf_mul_bits(XP[256 * k + b], reg, poly);
+                    }
+                }
+                const uint32_t old_be = mac == 8u ? w[9] : w[8];
+                digest = __builtin_bswap32(old_be) ^ reg;
+                const uint32_t new_be = __builtin_bswap32(digest);
+                if (!out_frames) {
+                    // in place: header bytes 16..23 and the digest's low word (CRC32's high word is
+                    // zero in a frame that is OK and stays)
+                    uint8_t* q = f + 32u + (mac - 4u);
+                    if ((((uintptr_t)f) & 3u) == 0) {
+                        reinterpret_cast<uint32_t*>(f)[4] = n4;
+                        reinterpret_cast<uint32_t*>(f)[5] = n5;
+                        *reinterpret_cast<uint32_t*>(q) = new_be;
+                    } else {
+                        for (int k = 0; k < 4; ++k) {
+                            f[16 + k] = (uint8_t)(n4 >> (8 * k));
+                            f[20 + k] = (uint8_t)(n5 >> (8 * k));
+                            q[k] = (uint8_t)(new_be >> (8 * k));
+                        }
+                    }
+                } else {
+                    w[4] = n4;
+                    w[5] = n5;
+                    if (mac == 8u) w[9] = new_be;  // (w[8], the high word, is zero)
+                    else w[8] = new_be;
+                    if (packed) {
+                        uint32_t* d = fr + threadIdx.x * fw;
+#pragma unroll
+                        for (int k = 0; k < 9; ++k) d[k] = w[k];
+                        if (mac == 8u) d[9] = w[9];
+                    } else {
+                        uint8_t* g = out_frames + i * frame_stride;
+                        if ((((uintptr_t)g) & 3u) == 0) {
+#pragma unroll
+                            for (int k = 0; k < 9; ++k) reinterpret_cast<uint32_t*>(g)[k] = w[k];
+                            if (mac == 8u) reinterpret_cast<uint32_t*>(g)[9] = w[9];
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < 10; ++k)
+                                if ((uint32_t)k < fw)
+                                    for (int b = 0; b < 4; ++b) g[4 * k + b] = (uint8_t)(w[k] >> (8 * b));
+                        }
+                    }
+                }
+            }
+            if (digests) digests[i] = digest;
+        }
+        if (packed) {
+            okf[threadIdx.x] = ok ? 1u : 0u;
+            __syncthreads();
+            const uint32_t cnt = (uint32_t)(n - i0 < (uint64_t)kReframeBlock ? n - i0 : (uint64_t)kReframeBlock);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out_frames + i0 * frame_stride);
+            for (uint32_t k = threadIdx.x; k < cnt * fw; k += kReframeBlock)
+                if (okf[mac == 8u ? k / 10u : k / 9u]) dst[k] = fr[k];
+            __syncthreads();  // fr and okf are rebuilt by the next tile
+        }
+    }
+}
+
+// first_bad = n before a TRUSTED reframe_frame_kernel, whose blocks lower it with atomicMin
+__global__ void reframe_first_bad_kernel(uint64_t* first_bad, uint64_t n) { *first_bad = n; }
+
+// Verify step 1(one thread per framed entry [32 B header][mac][payload], DigestManager.java:226-283):
 // reads the header and the stored digest once — 16-byte loads when the frame is 16-byte aligned,
 // dword loads when 4-byte aligned, bytes otherwise — and writes everything step 3 needs, so that
 // step 3 touches no frame bytes:

@@ -118,7 +118,7 @@ void for_chunks(uint64_t n, const uint32_t* lens, Body&& body) {
     bool inline_run = threads == 1;
     if (!inline_run && n < 4096) {  // small batches: sum their bytes to decide
         uint64_t bytes = 0;
-        for (uint64_t i = 0; i < n; ++i) bytes += lens[i];
+        for (uint64_t i = 0; lens && i < n; ++i) bytes += lens[i];  // (no lengths: a few bytes per entry)
         inline_run = bytes < kInlineBytes;
     }
     if (inline_run) return body((uint64_t)0, n);
@@ -159,6 +159,53 @@ inline void put_be32(uint8_t* p, uint32_t v) {
 inline void put_be64(uint8_t* p, uint64_t v) {
     put_be32(p, (uint32_t)(v >> 32));
     put_be32(p + 4, (uint32_t)v);
+}
+
+// DigestManager.verifyDigest of one frame ($BK/proto/checksum/DigestManager.java:226-283), in its
+// order: too short (:229-235), digest = update(update(0, [0, 32)), [32 + mac, len)) against getInt(32)
+// / getLong(32) (:236-261), ledger id (:267-273), entry id (:275-281). payload = false: what the
+// header alone decides (CRC32's non-zero high digest word still fails; no payload byte is read).
+inline int32_t frame_status(int algo, uint32_t mac, int64_t ledger_id, int64_t entry_id, int id_checks,
+                            const uint8_t* f, uint32_t l, bool whole_pool, bool payload) {
+    if (l < 32u + mac) return 1;
+    const uint32_t hi = mac == 8u ? be32(f + 32) : 0u;
+    if (payload) {
+        uint32_t reg = crc_raw(algo, 0xFFFFFFFFu, f, 32);  // update(0, header)
+        reg = whole_pool ? fold(algo, reg, f + 32 + mac, l - 32u - mac) : crc_raw(algo, reg, f + 32 + mac, l - 32u - mac);
+        if (hi != 0u || ~reg != be32(f + 32 + (mac - 4u))) return 2;
+    } else if (hi != 0u) {
+        return 2;
+    }
+    const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
+    const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
+    if (id_checks < 2 && lid != ledger_id) return 3;
+    if (id_checks == 0 && eid != entry_id) return 4;
+    return 0;
+}
+
+// x^(8 * len) mod P, the last length's power kept: replicated fragments hold runs of equal lengths.
+struct PowCache {
+    uint64_t len = 0;
+    uint32_t xp = 0x80000000u;  // x^0
+    uint32_t get(int algo, uint64_t l) {
+        if (l != len) {
+            xp = gf2::xpow(algo, 8ull * l);
+            len = l;
+        }
+        return xp;
+    }
+};
+
+// A verified frame's digest under a new LAC, without its payload: CRC is affine over GF(2), so
+// crc(H' || P) = crc(H || P) ^ R(H ^ H') * x^(8 |P|), R(D) the register after folding the header
+// difference D from zero. D is non-zero in bytes 16..23 only: the fold starts there.
+inline uint32_t reframed_digest(int algo, uint32_t mac, const uint8_t* f, uint32_t l, const uint8_t* new_lac_be,
+                                PowCache& pw) {
+    uint8_t d[16] = {0};
+    for (int k = 0; k < 8; ++k) d[k] = f[16 + k] ^ new_lac_be[k];
+    uint32_t delta = crc_raw(algo, 0u, d, 16);
+    if (delta) delta = gf2::mul(algo, delta, pw.get(algo, l - 32u - mac));
+    return be32(f + 32 + (mac - 4u)) ^ delta;
 }
 
 }  // namespace
@@ -225,29 +272,15 @@ void crc_indexed(int algo, const uint8_t* base, const uint64_t* offsets, const u
             if (is_big(lens[i])) out[i] = ~fold(algo, ~(seeds ? seeds[i] : seed_all), base + offsets[i], lens[i]);
 }
 
-// DigestManager.verifyDigest ($BK/proto/checksum/DigestManager.java:226-283), in its order: too
-// short (:229-235), digest = update(update(0, [0, 32)), [32 + mac, len)) against getInt(32) /
-// getLong(32) (:236-261), ledger id (:267-273), entry id (:275-281).
+// DigestManager.verifyDigest per frame (frame_status).
 uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks,
                        const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
     const uint32_t mac = algo == 0 ? 4u : 8u;
     const bool split = split_on();
     std::atomic<bool> big{false};
     auto one = [&](uint64_t i, bool whole_pool) -> int32_t {
-        const uint32_t l = lens[i];
-        if (l < 32u + mac) return 1;
-        const uint8_t* f = frames[i];
-        uint32_t reg = crc_raw(algo, 0xFFFFFFFFu, f, 32);  // update(0, header)
-        reg = whole_pool ? fold(algo, reg, f + 32 + mac, l - 32u - mac) : crc_raw(algo, reg, f + 32 + mac, l - 32u - mac);
-        const uint32_t computed = ~reg;
-        const uint32_t hi = mac == 8u ? be32(f + 32) : 0u;
-        const uint32_t expect = be32(f + 32 + (mac - 4u));
-        const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
-        const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
-        if (hi != 0u || computed != expect) return 2;
-        if (id_checks < 2 && lid != ledger_id) return 3;
-        if (id_checks == 0 && eid != first_entry_id + (int64_t)i) return 4;
-        return 0;
+        return frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, frames[i], lens[i],
+                            whole_pool, true);
     };
     std::atomic<uint64_t> first_bad{n};
     auto note_bad = [&](uint64_t bad) {
@@ -311,6 +344,74 @@ void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const
     if (big.load())
         for (uint64_t i = 0; i < n; ++i)
             if (is_big(lens[i])) one(i, true);
+}
+
+// LedgerFragmentReplicator's second framing of an entry it has read and verified
+// ($BK/client/LedgerFragmentReplicator.java:436-442, 506-511: the same ids, length and payload, the
+// ledger's current LAC): verifyDigest per frame (the header's part only when `trusted`), then the new
+// LAC and the digest by reframed_digest into the frames that are OK. One pass over a payload at most.
+uint64_t reframe_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks, bool trusted,
+                        uint8_t* const* frames, const uint32_t* lens, uint64_t n, const int64_t* new_lacs,
+                        uint32_t* digests, int32_t* status) {
+    const uint32_t mac = algo == 0 ? 4u : 8u;
+    const bool split = split_on() && !trusted;  // a trusted frame's payload is not read: nothing to split
+    std::atomic<bool> big{false};
+    auto one = [&](uint64_t i, bool whole_pool, PowCache& pw) -> int32_t {
+        uint8_t* f = frames[i];
+        const int32_t st = frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, f, lens[i],
+                                        whole_pool, !trusted);
+        uint32_t d = 0u;
+        if (st == 0) {
+            uint8_t lac[8];
+            put_be64(lac, (uint64_t)new_lacs[i]);
+            d = reframed_digest(algo, mac, f, lens[i], lac, pw);
+            memcpy(f + 16, lac, 8);
+            put_be32(f + 32 + (mac - 4u), d);  // (CRC32's high word is zero in a frame that is OK)
+        }
+        if (digests) digests[i] = d;
+        return st;
+    };
+    std::atomic<uint64_t> first_bad{n};
+    auto note_bad = [&](uint64_t bad) {
+        uint64_t cur = first_bad.load(std::memory_order_relaxed);
+        while (bad < cur && !first_bad.compare_exchange_weak(cur, bad, std::memory_order_relaxed)) {
+        }
+    };
+    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
+        uint64_t bad = n;
+        PowCache pw;
+        for (uint64_t i = i0; i < i1; ++i) {
+            if (split && is_big(lens[i])) {
+                big.store(true, std::memory_order_relaxed);
+                continue;
+            }
+            const int32_t st = one(i, false, pw);
+            status[i] = st;
+            if (st != 0 && i < bad) bad = i;
+        }
+        note_bad(bad);
+    });
+    if (big.load()) {
+        PowCache pw;
+        for (uint64_t i = 0; i < n; ++i)
+            if (is_big(lens[i])) {
+                status[i] = one(i, true, pw);
+                if (status[i] != 0) note_bad(i);
+            }
+    }
+    return first_bad.load();
+}
+
+void apply_reframe(int algo, uint8_t* const* frames, uint64_t n, const int64_t* new_lacs, const int32_t* status,
+                   const uint32_t* digests) {
+    const uint32_t mac = algo == 0 ? 4u : 8u;
+    for_chunks(n, nullptr, [&](uint64_t i0, uint64_t i1) {
+        for (uint64_t i = i0; i < i1; ++i) {
+            if (status[i] != 0) continue;
+            put_be64(frames[i] + 16, (uint64_t)new_lacs[i]);
+            put_be32(frames[i] + 32 + (mac - 4u), digests[i]);
+        }
+    });
 }
 
 }  // namespace host

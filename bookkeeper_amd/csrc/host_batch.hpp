@@ -67,6 +67,16 @@ uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int 
 void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                     const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
                     uint8_t* frames, uint64_t stride, uint32_t* digests);
+// Re-frames verified frames in place with new LACs (LedgerFragmentReplicator.java:436-442): status as
+// verify_frames (trusted: from the header alone, no payload byte read); a frame that is OK gets
+// new_lacs[i] at bytes 16..23 and the digest old ^ R(LAC difference) * x^(8 * payload length); the
+// others stay untouched with digests[i] = 0 (digests may be null). Returns the first failing index.
+uint64_t reframe_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks, bool trusted,
+                        uint8_t* const* frames, const uint32_t* lens, uint64_t n, const int64_t* new_lacs,
+                        uint32_t* digests, int32_t* status);
+// The GPU route's last step: writes new_lacs[i] and digests[i] into every frame whose status is 0.
+void apply_reframe(int algo, uint8_t* const* frames, uint64_t n, const int64_t* new_lacs, const int32_t* status,
+                   const uint32_t* digests);
 
 }  // namespace host
 }  // namespace bkd

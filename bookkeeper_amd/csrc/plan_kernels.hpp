@@ -466,17 +466,7 @@ struct PlanDirectSrc {
     }
 };
 
-// a * b mod P, bitwise (no tables): 32 shift/xor steps, for the few products per entry that have
-// no operator table (x^(-8*pad), powers of X).
-__device__ __forceinline__ uint32_t gf_mul_bits(uint32_t a, uint32_t b, uint32_t poly) {
-    uint32_t prod = 0u, cur = b;
-#pragma unroll
-    for (int k = 31; k >= 0; --k) {
-        prod ^= ((a >> k) & 1u) ? cur : 0u;
-        cur = (cur >> 1) ^ ((cur & 1u) ? poly : 0u);
-    }
-    return prod;
-}
+// (gf_mul_bits, the bitwise product a * b mod P, is in crc_kernels.hpp: reframe_frame_kernel uses it too)
 
 __device__ __forceinline__ uint32_t gf_pow_bits(uint32_t x, uint32_t e, uint32_t poly) {
     uint32_t r = 0x80000000u;  // x^0

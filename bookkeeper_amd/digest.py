@@ -22,7 +22,7 @@ import numpy as np
 from . import checksum as _ck
 from .bytebuf import CompositeBuffer
 from ._native import (CRC32, CRC32C, VERIFY_DIGEST_MISMATCH, VERIFY_ENTRY_MISMATCH, VERIFY_LEDGER_MISMATCH,
-                      VERIFY_OK, VERIFY_TOO_SHORT, check, lib)
+                      VERIFY_OK, VERIFY_TOO_SHORT, REFRAME_TRUSTED, check, lib)
 
 METADATA_LENGTH = 32          # DigestManager.java:48
 LAC_METADATA_LENGTH = 16      # DigestManager.java:49
@@ -203,6 +203,45 @@ class DigestManager:
                 _ck._dev_ptr(first_bad, "first_bad"), _ck._stream_ptr(stream, framed)))
         return status, first_bad
 
+    def reframe_batch(self, framed, offsets, lengths, first_entry_id: int, new_lacs, *, out_frames=None,
+                      frame_stride=None, trusted: bool = False, skip_entry_check: bool = False, stream=None):
+        """LedgerFragmentReplicator's second framing (LedgerFragmentReplicator.java:436-442): verifies n
+        framed entries as ``verify_batch`` does and gives every entry that verified the LAC new_lacs[i]
+        and the digest that goes with it, computed from the old digest and the payload length alone
+        (CRC is affine over GF(2)): the payloads are read once, by the verify. ``trusted``: the caller
+        has verified these frames; no payload byte is read and the status covers only what the header
+        decides (too short, CRC32's high digest word, ids) — a frame whose stored digest was wrong gets
+        a digest that is wrong again. ``out_frames`` (uint8 tensor): the new [32 B header][digest] of
+        entry i at byte i * frame_stride (default 32 + mac); None: `framed` is rewritten in place
+        (bytes 16..23 and the digest of each frame; frames must not overlap). Entries that are not OK
+        are left untouched in either. Returns (status int32[n], first_bad int64[1], digests int32[n],
+        0 for entries that are not OK)."""
+        import torch
+        n = offsets.numel()
+        dev = framed.device
+        hl = METADATA_LENGTH + self.macCodeLength
+        stride = 0
+        if out_frames is not None:
+            stride = frame_stride or hl
+            if stride >= hl and n and out_frames.numel() * out_frames.element_size() < (n - 1) * stride + hl:
+                raise ValueError("out_frames is too small for n frames at this stride")
+        elif frame_stride is not None:
+            raise ValueError("frame_stride given without out_frames")
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        first_bad = torch.empty(1, dtype=torch.int64, device=dev)
+        digests = torch.empty(n, dtype=torch.int32, device=dev)
+        with _ck._on_device(framed):
+            check(lib().bkd_digest_reframe_batch(
+                self.algo, self.ledgerId, first_entry_id, int(skip_entry_check), REFRAME_TRUSTED if trusted else 0,
+                _ck._dev_ptr(framed, "framed"), framed.numel() * framed.element_size(),
+                _ck._dev_ptr(offsets, "offsets", torch.int64, dev),
+                _ck._dev_ptr(lengths, "lengths", _ck._u32_dtypes(), dev, n), n,
+                _ck._dev_ptr(new_lacs, "new_lacs", torch.int64, dev, n),
+                _ck._dev_ptr(out_frames, "out_frames", None, dev), stride, _ck._dev_ptr(digests, "digests"),
+                _ck._dev_ptr(status, "status"), _ck._dev_ptr(first_bad, "first_bad"),
+                _ck._stream_ptr(stream, framed)))
+        return status, first_bad, digests
+
     # ---- batch host path (new; entries in host memory, SURVEY §8f rows 1-2 / BASELINE config 5) ----
     def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
         """BatchedReadOp.complete over a ByteBufList (BatchedReadOp.java:164-190): `frames` is a
@@ -241,6 +280,33 @@ class DigestManager:
             vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
         del views
         return frames, digests
+
+    def reframe_batch_host(self, frames, first_entry_id: int, new_lacs, trusted: bool = False,
+                           skip_entry_check: bool = False):
+        """``reframe_batch`` for entries in host memory: `frames` is a sequence of writable host buffers
+        (bytearray, writable numpy arrays), each one framed entry, rewritten in place. Returns
+        (status int32[n], first_bad, digests uint32[n])."""
+        if any(isinstance(f, np.ndarray) and not f.flags.c_contiguous for f in frames):
+            raise TypeError("frames must be contiguous: they are re-framed in place")
+        views = [_ck._host_view(f) for f in frames]
+        if any(not v.flags.writeable for v in views):
+            raise TypeError("frames must be writable buffers: they are re-framed in place")
+        n = len(views)
+        lacs = np.ascontiguousarray(new_lacs, dtype=np.int64)
+        if lacs.size != n:
+            raise ValueError("new_lacs must have one element per frame")
+        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+        lens = np.array([v.size for v in views], dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        digests = np.zeros(n, dtype=np.uint32)
+        first_bad = ctypes.c_uint64(0)
+        vp = ctypes.c_void_p
+        check(lib().bkd_digest_reframe_batch_host(
+            self.algo, self.ledgerId, first_entry_id, int(skip_entry_check), REFRAME_TRUSTED if trusted else 0,
+            vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(lacs.ctypes.data), vp(digests.ctypes.data),
+            vp(status.ctypes.data), ctypes.byref(first_bad)))
+        del views
+        return status, int(first_bad.value), digests
 
 
 class CRC32CDigestManager(DigestManager):
@@ -285,4 +351,4 @@ class DummyDigestManager(DigestManager):
     def package_batch(self, *a, **k):
         raise NotImplementedError("DUMMY digests need no device work")
 
-    verify_batch = package_batch_host = verify_batch_host = package_batch
+    verify_batch = package_batch_host = verify_batch_host = reframe_batch = reframe_batch_host = package_batch

@@ -232,6 +232,45 @@ BKD_API int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int
                                           const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
                                           void* h_frames, uint64_t frame_stride, uint32_t* h_digests);
 
+/* ---- re-framing verified entries with a new LAC (re-replication) -----------------------
+ * LedgerFragmentReplicator frames every entry it has just read and verified a second time with the
+ * ledger's current LAC: computeDigestAndPackageForSending(entryId, lh.getLastAddConfirmed(),
+ * entry.getLength(), data, ...) ($BK/client/LedgerFragmentReplicator.java:436-442, 506-511) — the same
+ * ledger id, entry id, length field and payload. CRC is affine over GF(2): for headers H, H' of equal
+ * length, crc(H' || P) = crc(H || P) ^ R(H ^ H') * x^(8 |P|) (mod P), R(D) the register after folding
+ * D from a zero register. So a frame that verified is re-framed from its old header, its stored digest,
+ * the new LAC and the payload LENGTH: no payload byte is read again.
+ *
+ * Entry i is the framed buffer of bkd_digest_verify_batch. Default (flags == 0): the call verifies
+ * exactly as bkd_digest_verify_batch does (d_status, *d_first_bad bit for bit the same), then re-frames
+ * every entry whose status is BKD_VERIFY_OK. BKD_REFRAME_TRUSTED: the caller has verified these frames
+ * (the usual flow: the read op did); no payload byte is read and no digest recomputed, the status is
+ * what the header alone decides in verifyDigest's order (1 too short / out of range, 2 a non-zero high
+ * word of CRC32's 8-byte digest, 3 / 4 the id checks) — a frame whose stored digest was wrong gets a
+ * digest that is wrong again.
+ * Output, OK entries only (no byte of any other entry's frame or out-frame is written):
+ *   apart    (d_out_frames != NULL): [32 B header with d_new_lacs[i]][digest] at d_out_frames +
+ *            i*frame_stride (frame_stride >= 32 + mac; the range must not overlap d_framed);
+ *   in place (d_out_frames == NULL): header bytes 16..23 and the digest of the frame itself. Frames
+ *            must not overlap one another: the result for overlapping frames is undefined.
+ * d_digests (may be NULL): the new digest per entry, 0 for an entry that is not OK.
+ * Device pointers; asynchronous on `stream`; no host synchronisation. */
+#define BKD_REFRAME_TRUSTED 1u /* do not recompute digests: the caller verified these frames */
+BKD_API int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check,
+                                     uint32_t flags, void* d_framed, uint64_t framed_size,
+                                     const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                     const int64_t* d_new_lacs, void* d_out_frames, uint64_t frame_stride,
+                                     uint32_t* d_digests, int32_t* d_status, uint64_t* d_first_bad, void* stream);
+/* Host-resident: entry i is its own writable host buffer h_frames[i] of h_lengths[i] bytes, re-framed in
+ * place. Route as bkd_digest_verify_batch_host (bkd_set_host_batch_route). CPU: verifyDigest's arithmetic
+ * per entry (skipped when trusted), then the GF(2) correction — one payload pass at most, and it needs
+ * no device. GPU: staged as verify; status and digests come back and the host writes each OK frame's
+ * 8 LAC bytes and digest. Synchronous. h_digests may be NULL. */
+BKD_API int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check,
+                                          uint32_t flags, void* const* h_frames, const uint32_t* h_lengths,
+                                          uint64_t n, const int64_t* h_new_lacs, uint32_t* h_digests,
+                                          int32_t* h_status, uint64_t* h_first_bad);
+
 /* ---- bookie-side entry-log scrub (§8f row 4) ------------------------------------------
  * An entry log is a 1024-byte file header (LOGFILE_HEADER_SIZE, DefaultEntryLogger.java:256)
  * followed by records [int32 BE size][entry bytes], an entry starting with its BE ledger id.
