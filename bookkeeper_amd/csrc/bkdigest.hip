@@ -191,26 +191,16 @@ std::atomic<int> g_plan_pf{2};  // loads in flight per lane in the chunk kernel 
 // their own launch (4-lane groups, next entry loaded during the current one). 0 = none.
 constexpr int kSmallLanes = 4;
 constexpr uint32_t kSmallBytes4 = 16u * kSmallLanes * 3u;  // one register set per entry (4 lanes, PF = 2): 192 B
-#ifndef BKD_SMALL_WIDE
-#define BKD_SMALL_WIDE 8
-#endif
-constexpr int kSmallLanesWide = BKD_SMALL_WIDE;             // bounds above 192 B: 8 lanes, PF = 3 (16: 1 KiB)
+constexpr int kSmallLanesWide = 8;                         // bounds above 192 B: 8 lanes, PF = 3
 constexpr uint32_t kSmallMaxBytes = 16u * kSmallLanesWide * 4u;
 std::atomic<uint32_t> g_plan_small{kSmallBytes4};
 // Entries shorter than this skip the chunks: plan_combine computes them, one thread each. Longer
 // bounds cost more than they save on config 3's Zipf mix: 128 B took 36 us off the chunk kernel
 // and added 54 us to combine (random slice-by-16 lookups from 64 lanes conflict in LDS banks).
-#ifndef BKD_PLAN_SERIAL
-#define BKD_PLAN_SERIAL 16
-#endif
-std::atomic<uint32_t> g_plan_serial{BKD_PLAN_SERIAL};
-#ifndef BKD_SHORT_MEAN_MAX
-#define BKD_SHORT_MEAN_MAX 1024
-#endif
-std::atomic<uint64_t> g_short_mean_max{BKD_SHORT_MEAN_MAX};  // bytes of base buffer per entry (bkd_set_short_class_mean)
-#ifndef BKD_VERIFY_FUSED
-#define BKD_VERIFY_FUSED 1
-#endif
+constexpr uint32_t kPlanSerial = 16;
+std::atomic<uint32_t> g_plan_serial{kPlanSerial};
+constexpr uint64_t kShortMeanMax = 1024;
+std::atomic<uint64_t> g_short_mean_max{kShortMeanMax};  // bytes of base buffer per entry (bkd_set_short_class_mean)
 // Indexed batches whose base buffer is at most this size skip the plan (latency over balance).
 constexpr uint64_t kDirectMaxBytes = 256u << 10;
 
@@ -360,18 +350,13 @@ int auto_lanes(uint64_t mean_len, uint64_t n = UINT64_MAX, int cus = 256) {
     return g;
 }
 
-// Loads in flight per lane (register double buffer depth) and load cache policy; build-time
-// knobs so variants can be A/B-timed in one process (tools/tune.py).
+// Loads in flight per lane (register double buffer depth) and load cache policy: the two build-time
+// knobs, so that tools/tune.py can time its variants in one process.
 #ifndef BKD_PF
 #define BKD_PF 2
 #endif
 #ifndef BKD_NT
 #define BKD_NT 1
-#endif
-#ifndef BKD_PACKAGE_DIGEST_PASS
-// 1: package digests written into the frames by their own kernel; 0: by the payload groups
-// (PackageSrc), which measured 3 % slower on 1M x 4 KiB (profiles/r03m_ab_order*.log)
-#define BKD_PACKAGE_DIGEST_PASS 1
 #endif
 constexpr int kPF = BKD_PF;
 constexpr bool kNT = BKD_NT != 0;
@@ -447,18 +432,12 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
     pg.merge = (uint32_t)g_plan_merge.load();
     pg.serial = g_plan_serial.load();
     // chunks of <= kShortPF + 1 steps: the chunk kernel's short tail, three chunks in flight per
-    // group (short_chunks_loop; BKD_SHORT_TAIL=0 builds the single-prefetch schedule for A/B timing)
-#ifndef BKD_SHORT_TAIL
-#define BKD_SHORT_TAIL 1
-#endif
+    // group (short_chunks_loop)
     const int pf = g_plan_pf.load();
-    pg.jshort = BKD_SHORT_TAIL ? (uint32_t)bkd::kShortPF + 1u : 0u;
+    pg.jshort = (uint32_t)bkd::kShortPF + 1u;
     // 8-byte descriptors when the batch has one seed for every entry (its head register is then a
     // kernel argument) and the default loads in flight (PlanDesc8, crc_kernels.hpp)
-#ifndef BKD_PLAN_D8
-#define BKD_PLAN_D8 1
-#endif
-    pg.d8 = (BKD_PLAN_D8 && seeds == nullptr && size < bkd::kPlanMaxSize8 && pf == 2) ? 1u : 0u;
+    pg.d8 = (seeds == nullptr && size < bkd::kPlanMaxSize8 && pf == 2) ? 1u : 0u;
     pg.nbins = (pg.ch + pg.merge - 1u + pg.step - 1u) / pg.step + 1u;
     pg.step_sh = (uint32_t)__builtin_ctz(pg.step);
     pg.ch_sh = (pg.ch & (pg.ch - 1u)) == 0u ? (uint32_t)__builtin_ctz(pg.ch) : 0xFFu;
@@ -493,10 +472,7 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
     // entry's skip the chunks: the chunk kernel computes them whole, as the direct kernel would (PlanRun::uniform,
     // decided on the device: plan_count's per-block ballots, reduced by plan_scan). Only where the
     // direct kernel would use the plan's lane count.
-#ifndef BKD_DIRECT_GATE
-#define BKD_DIRECT_GATE 1
-#endif
-    const bool gate = BKD_DIRECT_GATE && pg.small == 0u && direct_gate && auto_lanes(size / n, n, ds.cus) == G;
+    const bool gate = pg.small == 0u && direct_gate && auto_lanes(size / n, n, ds.cus) == G;
     hipError_t e = sc.get(0, cv.used, st, &sb);
     if (e == hipSuccess) e = sc.flag(st, &err);
     if (e == hipSuccess && pg.small) e = sc.run_word(st, &run_word);
@@ -524,12 +500,9 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
                                dim3(bkd::kBlock), 0, st, base, ss, ds.tables[algo][lane_index(kSmallLanesWide)], err, 1);
         }
     }
-    // count / emit / combine walk their 1024-entry blocks in grid stride (BKD_PLAN_GRID blocks per CU;
-    // 0: one block per entry block)
-#ifndef BKD_PLAN_GRID
-#define BKD_PLAN_GRID 2
-#endif
-    const uint32_t pgrid = BKD_PLAN_GRID ? (uint32_t)BKD_PLAN_GRID * (uint32_t)ds.cus : 0xFFFFFFFFu;
+    // count / emit / combine walk their 1024-entry blocks in grid stride (kPlanGrid blocks per CU)
+    constexpr uint32_t kPlanGrid = 2;
+    const uint32_t pgrid = kPlanGrid * (uint32_t)ds.cus;
     const uint32_t cgrid = std::min((nb + bkd::kCountBlocks - 1u) / bkd::kCountBlocks, pgrid);
     hipLaunchKernelGGL(bkd::plan_count_kernel, dim3(cgrid), dim3(bkd::kPlanBlock), 0, st, offsets,
                        lengths, size, n, pg, blk, blive, nb, run, bok);
@@ -917,7 +890,7 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
 // ---- DigestManager batch framing: the device sequences shared by the device- and host-resident
 // entry points -------------------------------------------------------------------------------
 
-// Package, fused route (4..64-lane groups, frames apart from the payload; BKD_PACKAGE_FUSED): each lane group
+// Package, fused route (4..64-lane groups, frames apart from the payload): each lane group
 // builds its entry's header from the index arrays and folds header + payload in one pass, storing the
 // digest (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
 template <int G>
@@ -933,9 +906,10 @@ void launch_package_fused(DeviceState& ds, hipStream_t st, int algo, int64_t led
 }
 
 // Package: header kernel (32 B BE header, header CRC as the payload's seed) -> payload CRCs through
-// the direct kernel -> digest kernel (BE digest after the header; BKD_PACKAGE_DIGEST_PASS=0 has the
-// payload groups store it instead) — or the fused route above, which folds the header inside the
-// payload kernel. Out-of-range payload entries raise the stream's bounds flag.
+// the direct kernel -> digest kernel (BE digest after the header, in a pass of its own: the payload
+// groups storing it themselves measured 3 % slower on 1M x 4 KiB, profiles/r03m_ab_order*.log) — or
+// the fused route above, which folds the header inside the payload kernel. Out-of-range payload
+// entries raise the stream's bounds flag.
 int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_entry_ids,
                    const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
                    uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
@@ -951,16 +925,13 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
         if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("bounds flag: ") + hipGetErrorString(e));
     }
     const unsigned blocks = (unsigned)((n + 255) / 256);
-#ifndef BKD_PACKAGE_FUSED
-#define BKD_PACKAGE_FUSED 1
-#endif
     // The fused route when the frames are their own buffer (DigestManager's ByteBufList(header, data),
     // bench.py --config verify4k: 0.674 -> 0.659 ms per 1M 4 KiB entries); frames written in place in
     // front of their payloads keep the header-first route (0.821 vs 0.832 ms fused, profiles/r06r_*).
     const uint64_t fr0 = (uint64_t)(uintptr_t)d_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
     const uint64_t pl0 = (uint64_t)(uintptr_t)d_payload, pl1 = pl0 + payload_size;
     const bool frames_apart = fr1 <= pl0 || pl1 <= fr0;
-    if (BKD_PACKAGE_FUSED && lanes >= 4 && frames_apart) {
+    if (lanes >= 4 && frames_apart) {
         const uint8_t* pl = (const uint8_t*)d_payload;
         switch (lanes) {
             case 4: launch_package_fused<4>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
@@ -979,7 +950,6 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     hipLaunchKernelGGL(bkd::package_header_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, ledger_id, d_entry_ids,
                        d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
     BKD_HIP(hipGetLastError());
-#if BKD_PACKAGE_DIGEST_PASS
     bkd::IndexedSrc src{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests};
     int rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
     if (rc) return rc;
@@ -987,13 +957,6 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
                        (uint8_t*)d_frames, frame_stride, mac);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
-#else
-    // the payload groups write each frame's digest field themselves (PackageSrc)
-    (void)blocks;
-    bkd::PackageSrc src{{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests}, (uint8_t*)d_frames,
-                        frame_stride, mac};
-    return dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
-#endif
 }
 
 // Fused verify of near-uniform frames: one kernel per lane count (crc_verify_fused_kernel).
@@ -1046,7 +1009,7 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
     // could send them to the direct kernel, which ignores the gate, after the fused kernel ran)
     const int route = indexed_direct(framed_size) ? 0 : 1;
     const int fused_lanes = auto_lanes(framed_size / n, n, ds.cus);
-    const bool fused = BKD_VERIFY_FUSED && route == 1 && fused_lanes == g_plan_lanes.load();
+    const bool fused = route == 1 && fused_lanes == g_plan_lanes.load();
     uint32_t* vflag = nullptr;
     uint32_t vepoch = 0;
     if (fused) {

@@ -36,18 +36,15 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBlock = 1024;          // 16 waves per CU, one workgroup per CU (LDS-limited)
 constexpr uint32_t kMainBytes = 131072u;  // 4 tables x 256 entries x 32 banks x 4 B
 
-#ifndef BKD_LANE_POS
-#define BKD_LANE_POS 1  // groups of 4 / 8 lanes finish by lane-position tables + DPP XOR (finish_lanes)
-#endif
-
 template <int G>
 struct Geo {
     static_assert(G == 1 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "group width");
     static constexpr int kLevels = G == 1 ? 0 : G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : 6;
     // Groups of <= 16 lanes sit inside one DPP row and have LDS room for the x^64/x^96 sets.
     static constexpr bool kFast = G <= 16;
-    // Groups of 4 / 8 lanes also stage the lane-position nibble tables (crc_tables.hpp).
-    static constexpr bool kLaneTab = BKD_LANE_POS && (G == 4 || G == 8);
+    // Groups of 4 / 8 lanes also stage the lane-position nibble tables (crc_tables.hpp) and finish
+    // by them + a DPP XOR (finish_lanes).
+    static constexpr bool kLaneTab = G == 4 || G == 8;
     static constexpr int kCompactWords = (2 + kLevels) * 1024 + 256 + 2048 + (kLaneTab ? 128 * G : 0);
     static constexpr int kAuxWords = kCompactWords - 1024 - (kFast ? 0 : 2048);  // staged after the main set
     static constexpr uint32_t kX32Off = kMainBytes;  // LDS byte offset of the x^32 set
@@ -68,20 +65,6 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
     return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
-#ifndef BKD_EARLY_PREFETCH
-#define BKD_EARLY_PREFETCH 0
-#endif
-#ifndef BKD_TAIL_UNCOND
-#define BKD_TAIL_UNCOND 0  // build-time variant: unconditional tail loads in the A/B fold loops
-#endif
-#ifndef BKD_CHUNK_UNROLL
-#define BKD_CHUNK_UNROLL 2  // chunk halves per iteration of the chunk kernel's loop (2, 4 or 8)
-#endif
-
-#ifndef BKD_MAIN_XOR3
-#define BKD_MAIN_XOR3 0  // build-time variant: the main fold's five-way XOR as two v_bitop3 (tools/ab_libs.py)
-#endif
-
 // v * C_main via the replicated tables. lanereg = 4*(lane&31) | 1<<16.
 // v_perm_b32 result bytes (b3..b0) = (0, hi, v.byte_t, 4*(lane&31)); hi = 1 selects the
 // upper 64 KiB half (tables 2, 3); the +128 immediate selects the odd table of a pair.
@@ -91,24 +74,11 @@ __device__ __forceinline__ uint32_t mul_main_add(const uint32_t* lds, uint32_t v
     const uint32_t a1 = __builtin_amdgcn_perm(v, lanereg, 0x0C0C0500u);
     const uint32_t a2 = __builtin_amdgcn_perm(v, lanereg, 0x0C020600u);
     const uint32_t a3 = __builtin_amdgcn_perm(v, lanereg, 0x0C020700u);
-#if BKD_MAIN_XOR3
-    return xor3(xor3(lds_word(lds, a0), lds_word(lds, a1 + 128u), lds_word(lds, a2)), lds_word(lds, a3 + 128u), d);
-#else
     // plain XORs: consumed in issue order (a v_bitop3 here measured up to 10 % slower on short entries)
     return lds_word(lds, a0) ^ lds_word(lds, a1 + 128u) ^ lds_word(lds, a2) ^ lds_word(lds, a3 + 128u) ^ d;
-#endif
 }
 
-#ifndef BKD_W0_CACHED
-#define BKD_W0_CACHED 0  // 1: every chunk's first block is a cached load (A/B)
-#endif
-#ifndef BKD_CLOCK_ADAPT
-#define BKD_CLOCK_ADAPT 1  // 0: the one-entry-per-group fold always uses mul_main_add
-#endif
-#ifndef BKD_LOW_CLOCK_MHZ
-#define BKD_LOW_CLOCK_MHZ 2000
-#endif
-constexpr uint64_t kLowClockMHz = BKD_LOW_CLOCK_MHZ;
+constexpr uint64_t kLowClockMHz = 2000;
 
 // One fold step of the four dword streams, c_k = c_k * C_main ^ d_k, with all 16 table lookups in
 // flight at once and the XORs as v_bitop3: the compiler's schedule (mul_main_add) issues them 8 at
@@ -171,10 +141,6 @@ __device__ __forceinline__ void fold4_main(uint32_t& c0, uint32_t& c1, uint32_t&
     c1 = xor3(xor3(t[4], t[5], t[6]), t[7], d1);
     c2 = xor3(xor3(t[8], t[9], t[10]), t[11], d2);
     c3 = xor3(xor3(t[12], t[13], t[14]), t[15], d3);
-}
-
-__device__ __forceinline__ uint32_t mul_main(const uint32_t* lds, uint32_t v, uint32_t lanereg) {
-    return mul_main_add(lds, v, lanereg, 0u);
 }
 
 // v * C via a compact 4x256 operator set at LDS byte offset `off`.
@@ -297,25 +263,6 @@ __device__ __forceinline__ void put_frame_digest(uint8_t* f, uint32_t digest, ui
     }
 }
 
-// Package payloads: IndexedSrc whose results (seeded with the header CRCs) are also written into
-// each frame's digest field by the group that computed them (the BKD_PACKAGE_DIGEST_PASS=0 build:
-// 3 % slower than the separate digest pass).
-struct PackageSrc : IndexedSrc {
-    uint8_t* frames;
-    uint64_t stride;
-    uint32_t mac;
-};
-
-// Where a work item's result goes: *dst, and for package payloads the frame's digest field too.
-template <class Src>
-__device__ __forceinline__ void put_result(const Src&, uint64_t, const Work& w, uint32_t v) {
-    *w.dst = v;
-}
-__device__ __forceinline__ void put_result(const PackageSrc& src, uint64_t i, const Work& w, uint32_t v) {
-    *w.dst = v;
-    put_frame_digest(src.frames + i * src.stride + 32, v, src.mac);
-}
-
 // Framed entry [32 B header][mac][payload]: CRC the payload resuming from the header CRC
 // already stored in seeds[i] (DigestManager.java:236-239); result over seeds[i] in place.
 struct FramedPayloadSrc {
@@ -418,9 +365,6 @@ __device__ __forceinline__ uint32_t finish_lanes(const uint32_t* lds, uint32_t c
         return mul_main_add(lds, c0, lanereg,
                             mul_aux_add(lds, Gm::kX96Off, c1, mul_aux_add(lds, Gm::kX64Off, c2, mul_aux(lds, Gm::kX32Off, c3))));
     } else if constexpr (Gm::kLaneTab) {
-#if BKD_FINISH_PROBE
-        return c0 ^ c1 ^ c2 ^ c3;  // measurement-only build: the finish's cost (wrong digests)
-#endif
         // one more product per lane, by its weight x^(128 (G-1-g)) in the group's register (eight
         // nibble lookups, independent), then an XOR over the group's lanes by DPP: one dependent
         // LDS round trip instead of log2(G)
@@ -476,6 +420,18 @@ __device__ __forceinline__ void stage_tables(uint32_t* lds, const uint32_t* __re
     __syncthreads();
 }
 
+// stage_tables, and the shader clock measured over it (shader cycles against the 100 MHz real-time
+// counter, both scalar reads): whether the one-entry-per-group fold takes fold4_main in this launch.
+// sched: 0 when the clock is below kLowClockMHz, 1 never, 2 always (bkd_set_fold_schedule).
+template <int G>
+__device__ __forceinline__ bool stage_tables_low_clock(uint32_t* lds, const uint32_t* __restrict__ tables, int sched) {
+    const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+    stage_tables<G>(lds, tables);
+    const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
+    return lds_image_at_zero(lds) &&
+           (sched == 2 || (sched == 0 && (clk1 - clk0) * 100u < (rt1 - rt0) * kLowClockMHz));
+}
+
 // Raw CRC register of base[s, e) (e - s >= 16 unless ALIGNED), with the register r0 folded into
 // its first 4 bytes, computed by the G lanes of one group; the result is valid in lane g == 0.
 // ALIGNED: `e` is 16-byte aligned in device memory, so every lane address is aligned; the lane
@@ -502,7 +458,7 @@ struct IsLateSeed : std::false_type {};
 template <class F>
 struct IsLateSeed<LateSeed<F>> : std::true_type {};
 
-template <int G, int PF, bool NT, bool ALIGNED, bool TAILU = BKD_TAIL_UNCOND != 0, bool B16 = false, class R0 = uint32_t>
+template <int G, int PF, bool NT, bool ALIGNED, bool TAILU = false, bool B16 = false, class R0 = uint32_t>
 __device__ __forceinline__ uint32_t fold_range(const uint32_t* lds, uint32_t lanereg, int g,
                                                const uint8_t* __restrict__ base, int64_t s, int64_t e, R0 r0src) {
     using Gm = Geo<G>;
@@ -648,7 +604,7 @@ __device__ __forceinline__ void groups_loop(const uint32_t* lds, uint32_t lanere
         const int st = src.get(i, wk);
         if (st != 0) {
             if (g == 0 && st != 3) {
-                put_result(src, i, wk, 0u);
+                *wk.dst = 0u;
                 if (st == 2 && err) atomicOr(err, 1u);
             }
             continue;
@@ -659,15 +615,15 @@ __device__ __forceinline__ void groups_loop(const uint32_t* lds, uint32_t lanere
                 const uint8_t* q = base + wk.s;
                 for (uint32_t k = 0; k < wk.len; ++k)
                     r = lds_word(lds, Gm::kByteTabOff + (((r ^ q[k]) & 0xffu) << 2)) ^ (r >> 8);
-                put_result(src, i, wk, r ^ wk.xorout);
+                *wk.dst = r ^ wk.xorout;
             }
             continue;
         }
-        constexpr bool kTailU = BKD_TAIL_UNCOND != 0 || std::is_same<Src, UniformLongSrc>::value;
+        constexpr bool kTailU = std::is_same<Src, UniformLongSrc>::value;
         const uint32_t v =
             low_clock ? fold_range<G, PF, NT, false, kTailU, true>(lds, lanereg, g, base, wk.s, wk.s + (int64_t)wk.len, wk.r0)
                       : fold_range<G, PF, NT, false, kTailU, false>(lds, lanereg, g, base, wk.s, wk.s + (int64_t)wk.len, wk.r0);
-        if (g == 0) put_result(src, i, wk, v ^ wk.xorout);
+        if (g == 0) *wk.dst = v ^ wk.xorout;
     }
 }
 
@@ -678,20 +634,11 @@ __device__ __forceinline__ void groups_loop(const uint32_t* lds, uint32_t lanere
 // So a group's result of round r (item gid + r·ngroups) moves to lane r mod G of the group
 // (ds_bpermute from the group's lane 0) and stays in a register until K·G rounds are held; then
 // every lane stores its K words at once, and the rest when the group's loop ends.
-#ifndef BKD_HOLD_STORE
-#define BKD_HOLD_STORE 8  // K: words held per lane (0: each round stores its result)
-#endif
-
-#ifndef BKD_HOLD_LONGLOOP
-#define BKD_HOLD_LONGLOOP 8  // the chunk kernel's long loop: 64 rounds per flush (config 3: ~60), 128 VGPRs
-#endif
-#ifndef BKD_SHORT_FIRST
-#define BKD_SHORT_FIRST 1  // Zipf -0.5 %, its < 1 KiB bucket alone +0.7 to +1.1 % (profiles/r06bm_bn_*)
-#endif
-#ifndef BKD_HOLD_SHORT
-#define BKD_HOLD_SHORT 2  // the chunk kernel's short tail: K·G = 16 rounds per group (config 3: ~15)
-#endif
-constexpr int kHoldLong = 32;  // words held per lane in the uniform kernel for batches of > 8·G rounds
+constexpr int kHoldStore = 8;      // K: words held per lane in the one-entry-per-group kernels
+constexpr int kHoldLong = 32;      // words held per lane in the uniform kernel for batches of > 8·G rounds
+constexpr int kHoldLongLoop = 8;   // the chunk kernel's long loop: 64 rounds per flush (config 3: ~60), 128 VGPRs
+constexpr int kHoldShort = 2;      // the chunk kernel's short tail: K·G = 16 rounds per group (config 3: ~15)
+constexpr int kHoldDirect = 4;     // the chunk kernel's near-uniform direct loop (32 rounds per flush)
 
 template <int G, int K>
 struct HeldResults {
@@ -761,9 +708,6 @@ __device__ __forceinline__ void held_store_loop(const uint32_t* lds, uint32_t la
 
 // Every work item of `src` written (no item left to another launch: PlanDirectSrc with `all`), results
 // held (HeldResults): out-of-range items 0 (and the bounds flag), items under 16 bytes serially.
-#ifndef BKD_HOLD_DIRECT
-#define BKD_HOLD_DIRECT 4  // the chunk kernel's near-uniform direct loop (32 rounds per flush)
-#endif
 template <int G, int PF, bool NT, int K, class Src>
 __device__ __forceinline__ void held_direct_loop(const uint32_t* lds, uint32_t lanereg, int g,
                                                  const uint8_t* __restrict__ base, const Src& src, uint64_t n,
@@ -783,8 +727,8 @@ __device__ __forceinline__ void held_direct_loop(const uint32_t* lds, uint32_t l
                 r = lds_word(lds, Gm::kByteTabOff + (((r ^ q[k]) & 0xffu) << 2)) ^ (r >> 8);
             v = r ^ wk.xorout;
         } else {
-            v = fold_range<G, PF, NT, false, BKD_TAIL_UNCOND != 0, false>(lds, lanereg, g, base, wk.s,
-                                                                         wk.s + (int64_t)wk.len, wk.r0) ^ wk.xorout;
+            v = fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, wk.s, wk.s + (int64_t)wk.len, wk.r0) ^
+                wk.xorout;
         }
         held.put(v, g, src.out, gid, ngroups, n);
     }
@@ -1050,14 +994,7 @@ __global__ void __launch_bounds__(kBlock) crc_groups_kernel(const uint8_t* __res
     __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
     const uint64_t n = src.count();
     if (n == 0) return;
-    // the shader clock over the table staging (shader cycles against the 100 MHz real-time counter,
-    // both scalar reads): below kLowClockMHz the one-entry-per-group fold takes fold4_main
-    const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-    stage_tables<G>(lds, tables);
-    const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-    const bool low_clock = lds_image_at_zero(lds) &&
-                           (sched == 2 || (sched == 0 && BKD_CLOCK_ADAPT &&
-                                           (clk1 - clk0) * 100u < (rt1 - rt0) * (uint64_t)kLowClockMHz));
+    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
 
     const int lane = threadIdx.x & 63;
     const int g = lane & (G - 1);
@@ -1075,12 +1012,12 @@ __global__ void __launch_bounds__(kBlock) crc_groups_kernel(const uint8_t* __res
         // entries past the short loop and below UniformLongSrc's 32 steps, results held as there:
         // 512 B -11 %, 1 KiB -7 %, 2 KiB -6 % (8-lane groups; profiles/r06aw_ax_*). (Held in the
         // short loop itself they cost 2-5 %: its entries are a few folds each.)
-        if (BKD_HOLD_STORE > 0 && src.len >= 16u) {
+        if (src.len >= 16u) {
             if (gid < n) {
-                if ((n + ngroups - 1) / ngroups <= (uint64_t)BKD_HOLD_STORE * G)
-                    held_store_loop<G, PF, NT, BKD_HOLD_STORE, BKD_TAIL_UNCOND != 0>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
+                if ((n + ngroups - 1) / ngroups <= (uint64_t)kHoldStore * G)
+                    held_store_loop<G, PF, NT, kHoldStore, false>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
                 else
-                    held_store_loop<G, PF, NT, kHoldLong, BKD_TAIL_UNCOND != 0>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
+                    held_store_loop<G, PF, NT, kHoldLong, false>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
             }
             return;
         }
@@ -1092,14 +1029,14 @@ __global__ void __launch_bounds__(kBlock) crc_groups_kernel(const uint8_t* __res
             else saw = indexed_small_loop<G, PF, NT, false>(lds, lanereg, g, base, src, n, gid, ngroups, err);
         }
         if (__any(saw) && (threadIdx.x & 63) == 0 && src.plan_flag) *src.plan_flag = src.plan_epoch;
-    } else if constexpr (std::is_same<Src, UniformLongSrc>::value && BKD_HOLD_STORE > 0) {
+    } else if constexpr (std::is_same<Src, UniformLongSrc>::value) {
         // (long uniform entries >= 16 B: no serial or out-of-range items)
         // K = 8 holds a group's 64 rounds (1M entries at 32 768 groups: 32); larger batches hold 32
         // words per lane so that they too store only at the end (8M: 256 rounds, -1.5 %; K = 32 for
         // 1M entries measured +0.3 to +0.8 %, profiles/r06aq_*, r06ar_*)
         if (gid < n) {
-            if ((n + ngroups - 1) / ngroups <= (uint64_t)BKD_HOLD_STORE * G)
-                held_store_loop<G, PF, NT, BKD_HOLD_STORE>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
+            if ((n + ngroups - 1) / ngroups <= (uint64_t)kHoldStore * G)
+                held_store_loop<G, PF, NT, kHoldStore>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
             else
                 held_store_loop<G, PF, NT, kHoldLong>(lds, lanereg, g, base, src, n, gid, ngroups, low_clock);
         }
@@ -1180,7 +1117,7 @@ __device__ __forceinline__ ChunkGeo chunk_geo(const PlanDesc8& d, int g, uint32_
     PlanDesc full;
     full.s_len = d.s_len & ~(1ull << kPlanHeadBit);
     full.r0 = ((d.s_len >> kPlanHeadBit) & 1u) ? r0h : 0u;
-    full.dst = 0u;
+    full.dst = 0u;  // unused for these descriptors: partials are stored by list position (HeldResults)
     return chunk_geo<G>(full, g);
 }
 
@@ -1188,7 +1125,7 @@ __device__ __forceinline__ ChunkGeo chunk_geo(const PlanDesc8& d, int g, uint32_
 template <int G, int PF, bool NT>
 __device__ __forceinline__ void chunk_prefetch(const uint8_t* __restrict__ base, const ChunkGeo& c, u32x4& W0,
                                                u32x4 (&A)[PF]) {
-    W0 = ld16<NT && !BKD_W0_CACHED>(base + c.la0);  // a head's first line is its neighbour's last
+    W0 = ld16<NT>(base + c.la0);
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
         const int64_t addr = (uint32_t)(k + 1) < c.J ? c.a + (int64_t)(k + 1) * Geo<G>::kStep : c.la0;
@@ -1196,27 +1133,10 @@ __device__ __forceinline__ void chunk_prefetch(const uint8_t* __restrict__ base,
     }
 }
 
-#ifndef BKD_SHORT_FOLD4
-// The short tail's folds with a step's 16 lookups requested before any is used (fold4_grouped; the
-// compiler's own schedule waited stream by stream there): two- and four-step chunks -0.9 / -2.6 %,
-// the < 1 KiB bucket -0.8 %, config 3 -0.1 % (round 6, profiles/r08o_ab_short_fold_grouped.log; the
-// inline-asm fold4_main, which needs the image at LDS address 0, measured alike: r08n_*)
-#define BKD_SHORT_FOLD4 1
-#endif
-#ifndef BKD_HOLE_GEO
-// The chunk kernel requests every geometry's blocks as they are: a hole has a window at base[0]
-// (skip_desc) and a chunk past the list the last real chunk's, so no geometry is selected per chunk
-// (0: the field-by-field selects of a "last real chunk" geometry). The < 1 KiB bucket -2.1 %,
-// 1M one-step chunks -1.6 %, 8 KiB chunk pairs -0.6 %, config 3 +-0, and the short tail's one
-// spilled register gone (round 6, profiles/r08h_ab_hole_geometry_full_static.log)
-#define BKD_HOLE_GEO 1
-#endif
-#ifndef BKD_FIRST_FAST
-// The chunk kernel's step-0 masks, seed image and pad removal as clamped shifts, no branches: bit 0
-// its short tail, bit 1 its long loop (0: the branchy form). 1M one-step chunks -6 %, the < 1 KiB
+// The chunk kernel's step-0 masks, seed image and pad removal are clamped shifts, no branches, in
+// its short tail and its long loop. Against the branchy form: 1M one-step chunks -6 %, the < 1 KiB
 // bucket -3.7 %, config 3 -0.3 % (round 6, profiles/r08b_ab_first_block_fast.log)
-#define BKD_FIRST_FAST 3
-#endif
+//
 // Dword k of a chunk's step-0 block, branch-free: x8 = 8 * (d0 - 4k) bits of it lie in front of the
 // chunk's first byte (cleared: low32(~0 << clamp(x8, 0, 32))), and it takes its part of the seed
 // image r0 << 8*d0 (low32((r0 : 0) >> (32 - clamp(x8, -32, 32))); a shift of 64 is 0 mod 64 and the
@@ -1245,32 +1165,8 @@ __device__ __forceinline__ u32x4 pad_junk_fast(u32x4 last, int32_t keep) {
 // image XORed in; fx = the part of the seed image that spills into step 1's dword 0.
 template <int G>
 __device__ __forceinline__ u32x4 chunk_first_block(const ChunkGeo& c, u32x4 W0, uint32_t& fx) {
-    using Gm = Geo<G>;
-#if BKD_FIRST_FAST & 1
-    fx = seed_part(c.r0, 8 * (c.d0 - Gm::kStep));
+    fx = seed_part(c.r0, 8 * (c.d0 - Geo<G>::kStep));
     return first_block_fast(W0, c.r0, c.d0);
-#endif
-    const int32_t d0 = c.d0;
-    u32x4 w;
-    if (d0 <= 0) w = W0;
-    else if (d0 < 16) w = mask_low_bytes(W0, (uint32_t)d0);
-    else w = u32x4{0u, 0u, 0u, 0u};
-    const uint32_t r0 = c.r0;
-    if (d0 > -4 && d0 < 16) {
-        // the seed image is r0 << 8*d0 across the 16-byte block: dword k = (r0:0 >> (32 + 32k - 8*d0))
-        const uint64_t R = (uint64_t)r0 << 32;
-        auto part = [&](int k) -> uint32_t {
-            const int32_t t = 32 + 32 * k - 8 * d0;
-            return (t > 0 && t < 64) ? (uint32_t)(R >> t) : 0u;
-        };
-        w.x ^= part(0);
-        w.y ^= part(1);
-        w.z ^= part(2);
-        w.w ^= part(3);
-    }
-    fx = 0u;
-    if (d0 > Gm::kStep - 4) fx = place_seed(r0, d0 - Gm::kStep);
-    return w;
 }
 
 // Raw register of a short chunk (J <= PF + 1: every block of it is in W0 and A[0..J-2]) — the
@@ -1282,29 +1178,21 @@ __device__ __forceinline__ uint32_t short_chunk_fold(const uint32_t* lds, uint32
     const u32x4 w = chunk_first_block<G>(c, W0, fx);
     uint32_t c0 = w.x, c1 = w.y, c2 = w.z, c3 = w.w;
     const uint32_t rem = c.J - 1u;
+    // a step's 16 lookups are requested before any is used (fold4_grouped; the compiler's own schedule
+    // of mul_main_add waited stream by stream here): two- and four-step chunks -0.9 / -2.6 %, the
+    // < 1 KiB bucket -0.8 %, config 3 -0.1 % (round 6, profiles/r08o_ab_short_fold_grouped.log; the
+    // inline-asm fold4_main, which needs the image at LDS address 0, measured alike: r08n_*)
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
-        if ((uint32_t)k < rem) {
-#if BKD_SHORT_FOLD4
+        if ((uint32_t)k < rem)
             fold4_grouped(lds, c0, c1, c2, c3, lanereg, A[k].x ^ (k == 0 ? fx : 0u), A[k].y, A[k].z, A[k].w);
-#else
-            c0 = mul_main_add(lds, c0, lanereg, A[k].x ^ (k == 0 ? fx : 0u));
-            c1 = mul_main_add(lds, c1, lanereg, A[k].y);
-            c2 = mul_main_add(lds, c2, lanereg, A[k].z);
-            c3 = mul_main_add(lds, c3, lanereg, A[k].w);
-#endif
-        }
     }
     if (c.pad && c.keep < 16) {  // the last step's bytes past the entry were folded last: XOR them out
         u32x4 last = W0;
 #pragma unroll
         for (int k = 0; k < PF; ++k)
             if ((uint32_t)k + 1u == rem) last = A[k];
-#if BKD_FIRST_FAST & 1
         const u32x4 junk = pad_junk_fast(last, c.keep);
-#else
-        const u32x4 junk = c.keep <= 0 ? last : mask_low_bytes(last, (uint32_t)c.keep);
-#endif
         c0 ^= junk.x;
         c1 ^= junk.y;
         c2 ^= junk.z;
@@ -1322,39 +1210,12 @@ __device__ __forceinline__ uint32_t chunk_fold(const uint32_t* lds, uint32_t lan
                                                u32x4 (&NA)[PF]) {
     using Gm = Geo<G>;
     const int64_t a = c.a;
-    const int32_t d0 = c.d0;
     const uint32_t rem = c.J - 1u;
-#if BKD_EARLY_PREFETCH
-    // the successor is requested before anything waits for this chunk's own blocks (unconditionally,
-    // so that the loads land in NW0/NA without a register copy): the compiler's s_waitcnt for W0 then
-    // sits after these loads, and consecutive chunks overlap their memory round trips instead of
-    // paying one each
-    chunk_prefetch<G, PF, NT>(base, nx, NW0, NA);
-#endif
-#if BKD_FIRST_FAST & 2
+    // (chunk_first_block's two values written out: through the helper the compiler allocates and
+    // schedules the long loop differently, and its measured schedule is kept as it is)
+    const int32_t d0 = c.d0;
     const u32x4 w = first_block_fast(W0, c.r0, d0);
     uint32_t fx = seed_part(c.r0, 8 * (d0 - Gm::kStep));
-#else
-    u32x4 w;
-    if (d0 <= 0) w = W0;
-    else if (d0 < 16) w = mask_low_bytes(W0, (uint32_t)d0);
-    else w = u32x4{0u, 0u, 0u, 0u};
-    const uint32_t r0 = c.r0;
-    if (d0 > -4 && d0 < 16) {
-        // the seed image is r0 << 8*d0 across the 16-byte block: dword k = (r0:0 >> (32 + 32k - 8*d0))
-        const uint64_t R = (uint64_t)r0 << 32;
-        auto part = [&](int k) -> uint32_t {
-            const int32_t t = 32 + 32 * k - 8 * d0;
-            return (t > 0 && t < 64) ? (uint32_t)(R >> t) : 0u;
-        };
-        w.x ^= part(0);
-        w.y ^= part(1);
-        w.z ^= part(2);
-        w.w ^= part(3);
-    }
-    uint32_t fx = 0u;
-    if (d0 > Gm::kStep - 4) fx = place_seed(r0, d0 - Gm::kStep);
-#endif
     uint32_t c0 = w.x, c1 = w.y, c2 = w.z, c3 = w.w;
     // the lane's last block as it was folded: a pad is XORed out of the very register that folded
     // it, so the bytes past the entry (another entry's, or past the caller's buffer) cancel whatever
@@ -1376,9 +1237,7 @@ __device__ __forceinline__ uint32_t chunk_fold(const uint32_t* lds, uint32_t lan
         c3 = mul_main_add(lds, c3, lanereg, (d).w);     \
     } while (0)
     if (rem <= (uint32_t)PF) {
-#if !BKD_EARLY_PREFETCH
         chunk_prefetch<G, PF, NT>(base, nx, NW0, NA);
-#endif
         if (rem > 0u) BKD_FOLD0(A[0]);
 #pragma unroll
         for (int k = 1; k < PF; ++k)
@@ -1420,9 +1279,7 @@ __device__ __forceinline__ uint32_t chunk_fold(const uint32_t* lds, uint32_t lan
 #pragma unroll
         for (int k = 0; k < PF; ++k)
             if ((uint32_t)(PF + k) < left) A[k] = ld16<NT>(p + (int64_t)(PF + k) * Gm::kStep);
-#if !BKD_EARLY_PREFETCH
         chunk_prefetch<G, PF, NT>(base, nx, NW0, NA);  // issued after every load of this chunk
-#endif
 #pragma unroll
         for (int k = 0; k < PF; ++k)
             if ((uint32_t)k < left) BKD_FOLD(B[k]);
@@ -1443,11 +1300,7 @@ __device__ __forceinline__ uint32_t chunk_fold(const uint32_t* lds, uint32_t lan
         // the last step's block of this lane ends past the entry: its bytes >= the entry's end were
         // folded last (XORed in after the final multiply), so XOR them out again
         const int32_t keep = c.keep;
-#if BKD_FIRST_FAST & 2
         const u32x4 junk = pad_junk_fast(last, keep);
-#else
-        const u32x4 junk = keep <= 0 ? last : mask_low_bytes(last, (uint32_t)keep);
-#endif
         c0 ^= junk.x;
         c1 ^= junk.y;
         c2 ^= junk.z;
@@ -1469,41 +1322,22 @@ __device__ __forceinline__ void short_chunks_loop(const uint32_t* lds, uint32_t 
                                                   uint32_t r0h,
                                                   uint64_t i, uint64_t n, uint64_t ngroups, uint32_t* __restrict__ out,
                                                   uint32_t* __restrict__ partials, uint64_t nstart) {
-#if BKD_HOLD_SHORT > 0
     // partials by list position, held (HeldResults; a final chunk's or a hole's word lands in its own
     // unused slot): the short tail is a group's last work, so they are stored at its very end
     const uint64_t gid0 = i - nstart;
-    HeldResults<G, BKD_HOLD_SHORT> held;
-#endif
+    HeldResults<G, kHoldShort> held;
     auto clampi = [&](uint64_t j) { return j < n ? j : n - 1; };
     auto geo_at = [&](uint64_t j) {
         ChunkGeo c = chunk_geo<G>(descs[clampi(j)], g, r0h);
         if (j >= n) c.len = 0;
         return c;
     };
-#if BKD_HOLE_GEO
     // every geometry has loadable blocks: a chunk past the list has the last real chunk's (clampi), a
-    // hole the window skip_desc() gives it at base[0]
+    // hole the window skip_desc() gives it at base[0], so no geometry is selected per chunk. Against
+    // field-by-field selects of a "last real chunk" geometry: the < 1 KiB bucket -2.1 %, 1M one-step
+    // chunks -1.6 %, 8 KiB chunk pairs -0.6 %, config 3 +-0, and the short tail's one spilled register
+    // gone (round 6, profiles/r08h_ab_hole_geometry_full_static.log)
     auto load = [&](const ChunkGeo& c, u32x4& W0, u32x4 (&A)[PF]) { chunk_prefetch<G, PF, NT>(base, c, W0, A); };
-#else
-    // blocks a hole (or a chunk past the list) loads instead: the last real chunk's, base[0, 16)
-    // before one is seen. Selected field by field: a reference to one of two geometries would put
-    // both in scratch memory.
-    int64_t fa = 0, fla0 = 0;
-    uint32_t fJ = 1u;
-    auto load = [&](const ChunkGeo& c, u32x4& W0, u32x4 (&A)[PF]) {
-        if (c.len) {
-            fa = c.a;
-            fla0 = c.la0;
-            fJ = c.J;
-        }
-        ChunkGeo t;
-        t.a = fa;
-        t.la0 = fla0;
-        t.J = fJ;
-        chunk_prefetch<G, PF, NT>(base, t, W0, A);
-    };
-#endif
     u32x4 W0x, Ax[PF], W0y, Ay[PF], W0z, Az[PF];
     ChunkGeo cx = geo_at(i), cy = geo_at(i + ngroups), cz = geo_at(i + 2 * ngroups);
     load(cx, W0x, Ax);
@@ -1511,21 +1345,11 @@ __device__ __forceinline__ void short_chunks_loop(const uint32_t* lds, uint32_t 
     load(cz, W0z, Az);
     Desc dx = descs[clampi(i + 3 * ngroups)], dy = descs[clampi(i + 4 * ngroups)],
          dz = descs[clampi(i + 5 * ngroups)];
-#if BKD_HOLD_SHORT > 0
-#define BKD_SHORT_EMIT(C, v)                                                                 \
-    held.put(v, g, partials + nstart, gid0, ngroups, n - nstart);                            \
-    if (g == 0 && C.len && (C.dst & kPlanFinal)) out[C.dst & ~kPlanFinal] = ~v;
-#else
-#define BKD_SHORT_EMIT(C, v)                                                                 \
-    if (g == 0 && C.len) {                                                                   \
-        if (C.dst & kPlanFinal) out[C.dst & ~kPlanFinal] = ~v;                               \
-        else partials[C.dst] = v;                                                            \
-    }
-#endif
 #define BKD_SHORT_STEP(C, W0C, AC, DC)                                                       \
     {                                                                                        \
         const uint32_t v = C.len ? short_chunk_fold<G, PF>(lds, lanereg, C, W0C, AC) : 0u;   \
-        BKD_SHORT_EMIT(C, v)                                                                 \
+        held.put(v, g, partials + nstart, gid0, ngroups, n - nstart);                        \
+        if (g == 0 && C.len && (C.dst & kPlanFinal)) out[C.dst & ~kPlanFinal] = ~v;          \
         C = chunk_geo<G>(DC, g, r0h); /* chunk i + 3 ngroups */                              \
         if (i + 3 * ngroups >= n) C.len = 0;                                                 \
         load(C, W0C, AC);                                                                    \
@@ -1541,10 +1365,7 @@ __device__ __forceinline__ void short_chunks_loop(const uint32_t* lds, uint32_t 
         BKD_SHORT_STEP(cz, W0z, Az, dz)
     }
 #undef BKD_SHORT_STEP
-#undef BKD_SHORT_EMIT
-#if BKD_HOLD_SHORT > 0
     held.finish(g, partials + nstart, gid0, ngroups, n - nstart);
-#endif
 }
 
 // Chunks [0, n) of the list in grid stride, one prefetched chunk per group (X/Y sets).
@@ -1555,23 +1376,12 @@ __device__ __forceinline__ void long_chunks_loop(const uint32_t* lds, uint32_t l
                                                  uint64_t n, uint64_t gid, uint64_t ngroups, uint32_t* __restrict__ out,
                                                  uint32_t* __restrict__ partials) {
     auto clampi = [&](uint64_t j) { return j < n ? j : n - 1; };
-    // a hole (len == 0) or a missing next chunk prefetches the current chunk's own blocks
-    auto pf_geo = [&](const ChunkGeo& nx, const ChunkGeo& cur) -> const ChunkGeo& { return nx.len ? nx : cur; };
-#if BKD_HOLD_LONGLOOP > 0
     // partials by list position, held (a final chunk's or a hole's word lands in its own unused slot)
-    HeldResults<G, BKD_HOLD_LONGLOOP> held;
+    HeldResults<G, kHoldLongLoop> held;
     auto emit = [&](const ChunkGeo& c, uint32_t v) {
         held.put(v, g, partials, gid, ngroups, n);
         if (g == 0 && c.len && (c.dst & kPlanFinal)) out[c.dst & ~kPlanFinal] = ~v;
     };
-#else
-    auto emit = [&](const ChunkGeo& c, uint32_t v) {
-        if (g == 0 && c.len) {
-            if (c.dst & kPlanFinal) out[c.dst & ~kPlanFinal] = ~v;
-            else partials[c.dst] = v;
-        }
-    };
-#endif
 
     u32x4 W0x, Ax[PF], Bx[PF], W0y, Ay[PF], By[PF];
     uint64_t i = gid;
@@ -1582,27 +1392,17 @@ __device__ __forceinline__ void long_chunks_loop(const uint32_t* lds, uint32_t l
     // load), and enough loads issued between a descriptor and its use that the compiler's count of
     // them never reaches back into the current chunk's prefetch.
     Desc dA = descs[clampi(i + ngroups)], dB = descs[clampi(i + 2 * ngroups)];
-#if BKD_HOLE_GEO
     // every geometry has loadable blocks (a hole's window is base[0], skip_desc; a missing next chunk
     // is the last real one, clampi): the next chunk's blocks are requested whatever it is
-#define BKD_PF_GEO(nx, cur) (nx)
     chunk_prefetch<G, PF, NT>(base, cur, W0x, Ax);
-#else
-    // a hole's prefetch reads base[0, 16) (only plans that overflowed their capacity have holes)
-    ChunkGeo safe;
-    safe.la0 = safe.a = 0, safe.J = 1;
-#define BKD_PF_GEO(nx, cur) pf_geo(nx, cur.len ? cur : safe)
-    chunk_prefetch<G, PF, NT>(base, cur.len ? cur : safe, W0x, Ax);
-#endif
 #define BKD_CHUNK_HALF(DN, W0C, AC, BC, W0N, AN)                                                            \
     {                                                                                                      \
         const bool more = i + ngroups < n;                                                                 \
         ChunkGeo nx = chunk_geo<G>(DN, g, r0h);                                                            \
         DN = descs[clampi(i + 3 * ngroups)];                                                               \
         if (!more) nx.len = 0;                                                                             \
-        const ChunkGeo& pg = BKD_PF_GEO(nx, cur);                                                          \
-        const uint32_t v = cur.len ? chunk_fold<G, PF, NT>(lds, lanereg, g, base, cur, W0C, AC, BC, pg, W0N, AN) \
-                                   : (chunk_prefetch<G, PF, NT>(base, pg, W0N, AN), 0u);                   \
+        const uint32_t v = cur.len ? chunk_fold<G, PF, NT>(lds, lanereg, g, base, cur, W0C, AC, BC, nx, W0N, AN) \
+                                   : (chunk_prefetch<G, PF, NT>(base, nx, W0N, AN), 0u);                   \
         emit(cur, v);                                                                                      \
         if (!more) break;                                                                                  \
         i += ngroups;                                                                                      \
@@ -1611,36 +1411,14 @@ __device__ __forceinline__ void long_chunks_loop(const uint32_t* lds, uint32_t l
     for (;;) {
         BKD_CHUNK_HALF(dA, W0x, Ax, Bx, W0y, Ay)  // chunk i in set X, prefetch into Y
         BKD_CHUNK_HALF(dB, W0y, Ay, By, W0x, Ax)  // chunk i in set Y, prefetch into X
-#if BKD_CHUNK_UNROLL >= 4
-        // the back edge copies the loop-carried descriptor registers, for which the compiler waits
-        // with s_waitcnt vmcnt(0) — a full drain of the loads in flight; more halves per iteration,
-        // fewer drains
-        BKD_CHUNK_HALF(dA, W0x, Ax, Bx, W0y, Ay)
-        BKD_CHUNK_HALF(dB, W0y, Ay, By, W0x, Ax)
-#endif
-#if BKD_CHUNK_UNROLL >= 8
-        BKD_CHUNK_HALF(dA, W0x, Ax, Bx, W0y, Ay)
-        BKD_CHUNK_HALF(dB, W0y, Ay, By, W0x, Ax)
-        BKD_CHUNK_HALF(dA, W0x, Ax, Bx, W0y, Ay)
-        BKD_CHUNK_HALF(dB, W0y, Ay, By, W0x, Ax)
-#endif
     }
-#if BKD_HOLD_LONGLOOP > 0
     held.finish(g, partials, gid, ngroups, n);
-#endif
 #undef BKD_CHUNK_HALF
-#undef BKD_PF_GEO
 }
 
 // Blocks per chunk in the short tail's register sets beside step 0: chunks of <= kShortPF + 1 steps
 // (PlanGeo::jshort) take short_chunks_loop.
-#ifndef BKD_SHORT_PF
-#define BKD_SHORT_PF 3
-#endif
-constexpr int kShortPF = BKD_SHORT_PF;
-#ifndef BKD_SHORT_NT
-#define BKD_SHORT_NT 0  // the short tail's loads are cached: heads share lines with their neighbours (1: nontemporal)
-#endif
+constexpr int kShortPF = 3;
 
 // The chunk list [0, n) (crc_plan_chunks_kernel): [0, nmain) by long_chunks_loop, then the short
 // tail [nmain, n) by short_chunks_loop (nmain == n: no short tail).
@@ -1650,19 +1428,14 @@ __device__ __forceinline__ void plan_chunks_loop(const uint32_t* lds, uint32_t l
                                                  uint32_t r0h,
                                                  uint64_t n, uint64_t nmain, uint64_t gid, uint64_t ngroups,
                                                  uint32_t* __restrict__ out, uint32_t* __restrict__ partials) {
-#if BKD_SHORT_FIRST
     // the short tail first: the long loop's held partials (the larger set) are then stored at the
-    // group's very end (per-group work, and so the kernel's balance, does not depend on the order)
+    // group's very end (per-group work, and so the kernel's balance, does not depend on the order):
+    // Zipf -0.5 %, its < 1 KiB bucket alone +0.7 to +1.1 % (profiles/r06bm_bn_*).
+    // The short tail's loads are cached: heads share lines with their neighbours.
     if (nmain < n && gid < n - nmain)
-        short_chunks_loop<G, kShortPF, NT && BKD_SHORT_NT>(lds, lanereg, g, base, descs, r0h, nmain + gid, n, ngroups, out,
-                                                          partials, nmain);
+        short_chunks_loop<G, kShortPF, false>(lds, lanereg, g, base, descs, r0h, nmain + gid, n, ngroups, out, partials,
+                                              nmain);
     if (gid < nmain) long_chunks_loop<G, PF, NT>(lds, lanereg, g, base, descs, r0h, nmain, gid, ngroups, out, partials);
-#else
-    if (gid < nmain) long_chunks_loop<G, PF, NT>(lds, lanereg, g, base, descs, r0h, nmain, gid, ngroups, out, partials);
-    if (nmain < n && gid < n - nmain)
-        short_chunks_loop<G, kShortPF, NT && BKD_SHORT_NT>(lds, lanereg, g, base, descs, r0h, nmain + gid, n, ngroups, out,
-                                                          partials, nmain);
-#endif
 }
 
 
@@ -1697,13 +1470,12 @@ __global__ void __launch_bounds__(kBlock) crc_plan_chunks_kernel(const uint8_t* 
     // count[1]: the list position of the first chunk of at most PF + 1 steps (plan_emit_kernel)
     const uint64_t nmain = n ? std::min<uint64_t>(n, count[1]) : 0u;
     if (gid < n) plan_chunks_loop<G, PF, NT>(lds, lanereg, g, base, descs, r0h, n, nmain, gid, ngroups, out, partials);
-#if BKD_HOLD_DIRECT > 0
     // near-uniform batches (every entry here, one per group): results held as the uniform kernel's
     if (nov && ov.all) {
-        if (gid < nov) held_direct_loop<G, PF, NT, BKD_HOLD_DIRECT>(lds, lanereg, g, base, ov, nov, gid, ngroups, err);
-    } else
-#endif
-    if (nov) groups_loop<G, PF, NT>(lds, lanereg, g, base, ov, nov, gid, ngroups, err);
+        if (gid < nov) held_direct_loop<G, PF, NT, kHoldDirect>(lds, lanereg, g, base, ov, nov, gid, ngroups, err);
+    } else if (nov) {
+        groups_loop<G, PF, NT>(lds, lanereg, g, base, ov, nov, gid, ngroups, err);
+    }
 }
 
 // ---- synthetic input: little-endian splitmix64 stream ----
@@ -2162,20 +1934,13 @@ __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
     uint32_t* __restrict__ digests, uint32_t* __restrict__ err, int sched) {
     using Gm = Geo<G>;
     __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
-    const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-    stage_tables<G>(lds, tables);
-    const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-    const bool low_clock = lds_image_at_zero(lds) &&
-                           (sched == 2 || (sched == 0 && BKD_CLOCK_ADAPT &&
-                                           (clk1 - clk0) * 100u < (rt1 - rt0) * (uint64_t)kLowClockMHz));
+    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
     const int lane = threadIdx.x & 63;
     const int g = lane & (G - 1);
     const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
     const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
     const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
-#if BKD_HOLD_STORE > 0
-    HeldResults<G, BKD_HOLD_STORE> held;
-#endif
+    HeldResults<G, kHoldStore> held;
     for (uint64_t i = gid; i < n; i += ngroups) {
         const uint64_t o = offsets[i];
         const uint32_t l = lengths[i];
@@ -2205,20 +1970,14 @@ __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
             } else {
                 const int64_t s = (int64_t)o, e = s + (int64_t)l;
                 const LateSeed<decltype(header_reg)> late{header_reg};
-                v = low_clock ? fold_range<G, PF, NT, false, BKD_TAIL_UNCOND != 0, true>(lds, lanereg, g, base, s, e, late)
-                              : fold_range<G, PF, NT, false, BKD_TAIL_UNCOND != 0, false>(lds, lanereg, g, base, s, e, late);
+                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, late)
+                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, late);
             }
             d = ~v;
         }
-#if BKD_HOLD_STORE > 0
         held.put(d, g, digests, gid, ngroups, n);
-#else
-        if (g == 0) digests[i] = d;
-#endif
     }
-#if BKD_HOLD_STORE > 0
     held.finish(g, digests, gid, ngroups, n);
-#endif
 }
 
 template <int G, int PF, bool NT>
@@ -2230,21 +1989,13 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
     using Gm = Geo<G>;
     if (*vflag == vepoch) return;  // some frame out of band: the header / plan / finish sequence runs
     __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
-    // payload fold schedule from the shader clock over the table staging (as crc_groups_kernel)
-    const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-    stage_tables<G>(lds, tables);
-    const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-    const bool low_clock = lds_image_at_zero(lds) &&
-                           (sched == 2 || (sched == 0 && BKD_CLOCK_ADAPT &&
-                                           (clk1 - clk0) * 100u < (rt1 - rt0) * (uint64_t)kLowClockMHz));
+    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
     const int lane = threadIdx.x & 63;
     const int g = lane & (G - 1);
     const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
     const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
     const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
-#if BKD_HOLD_STORE > 0
-    HeldResults<G, BKD_HOLD_STORE> held;
-#endif
+    HeldResults<G, kHoldStore> held;
     for (uint64_t i = gid; i < n; i += ngroups) {
         const uint64_t o = offsets[i];
         const uint32_t l = lengths[i];
@@ -2267,8 +2018,8 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
                 for (const uint8_t* q = base + s; q < base + e; ++q)
                     v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
             } else {
-                v = low_clock ? fold_range<G, PF, NT, false, BKD_TAIL_UNCOND != 0, true>(lds, lanereg, g, base, s, e, reg)
-                              : fold_range<G, PF, NT, false, BKD_TAIL_UNCOND != 0, false>(lds, lanereg, g, base, s, e, reg);
+                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, reg)
+                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, reg);
             }
             const uint32_t computed = ~v;
             // digest: 4-byte BE int (CRC32C) or 8-byte BE zero-extended long (CRC32) at offset 32
@@ -2287,19 +2038,10 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
             else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) st = 4;
             else st = 0;
         }
-#if BKD_HOLD_STORE > 0
         held.put((uint32_t)st, g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
         if (g == 0 && st != 0) atomicMin(first_bad, (unsigned long long)i);
-#else
-        if (g == 0) {
-            status[i] = st;
-            if (st != 0) atomicMin(first_bad, (unsigned long long)i);
-        }
-#endif
     }
-#if BKD_HOLD_STORE > 0
     held.finish(g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
-#endif
 }
 
 }  // namespace bkd

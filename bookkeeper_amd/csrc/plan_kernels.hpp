@@ -315,12 +315,10 @@ __device__ __forceinline__ PlanDesc chunk_desc_of(int64_t ae, int64_t s0, uint32
 // chunks of the block's entries form one contiguous run in the full bin, written by the whole
 // block (one descriptor per thread per pass, coalesced, no per-entry serial loop) — including
 // entries with thousands of chunks. Grid stride over the nb * reps virtual blocks.
-#ifndef BKD_PLAN_OCC
-#define BKD_PLAN_OCC 8
-#endif
 // emit and combine at 8 waves per SIMD (<= 64 VGPRs): two 1024-thread blocks per CU resident, as
-// BKD_PLAN_GRID launches them
-__global__ void __launch_bounds__(kPlanBlock, BKD_PLAN_OCC) plan_emit_kernel(const uint64_t* __restrict__ offsets,
+// launch_plan starts them (its kPlanGrid blocks per CU)
+constexpr int kPlanOcc = 8;
+__global__ void __launch_bounds__(kPlanBlock, kPlanOcc) plan_emit_kernel(const uint64_t* __restrict__ offsets,
                                                                const uint32_t* __restrict__ lengths,
                                                                const uint32_t* __restrict__ seeds, uint32_t seed_all,
                                                                uint64_t size, uint64_t n, PlanGeo pg,
@@ -584,7 +582,7 @@ __device__ __forceinline__ uint32_t strided_horner(const uint32_t* XT, const uin
     return r;
 }
 
-__global__ void __launch_bounds__(1024, BKD_PLAN_OCC) plan_combine_kernel(
+__global__ void __launch_bounds__(1024, kPlanOcc) plan_combine_kernel(
     const uint8_t* __restrict__ base, const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths,
     const uint32_t* __restrict__ seeds, uint32_t seed_all, uint64_t size, uint64_t n, PlanGeo pg,
     const uint32_t* __restrict__ xtab, const uint32_t* __restrict__ btab, const uint32_t* __restrict__ xinv, uint32_t poly,

@@ -1,5 +1,5 @@
 """CPU: the chunk kernel's branch-free step-0 block (crc_kernels.hpp first_block_fast / seed_part /
-pad_junk_fast, BKD_FIRST_FAST) against the branchy form it replaced (mask_low_bytes, the seed image
+pad_junk_fast) against the branchy form it replaced (mask_low_bytes, the seed image
 `part(k)` and place_seed), restated in Python and compared exhaustively over the offsets a lane can
 see: d0 (bytes of the lane's step-0 block in front of the chunk's first byte) and keep (bytes of its
 last block that belong to the chunk) from -1100 to 1100, every step width the lane groups use.
