@@ -17,9 +17,11 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <shared_mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bkdigest.h"
@@ -77,54 +79,20 @@ struct StreamScratch {
     // verify gate word (verify_gate_kernel) and the epoch of the latest verify on this stream
     uint32_t* vflag = nullptr;
     uint32_t vepoch = 0;
-    hipError_t vflag_word(hipStream_t st, uint32_t** out) {
-        if (!vflag) {
-            hipError_t e = hipMalloc((void**)&vflag, sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(vflag, 0, sizeof(uint32_t), st);
-            if (e != hipSuccess) {
-                vflag = nullptr;
-                return e;
-            }
-        }
-        *out = vflag;
-        return hipSuccess;
+    // One of the lazily made, zero-initialised device words above (err, run, uni, vflag).
+    hipError_t word(uint32_t*& w, hipStream_t st) {
+        if (w) return hipSuccess;
+        hipError_t e = hipMalloc((void**)&w, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemsetAsync(w, 0, sizeof(uint32_t), st);
+        if (e != hipSuccess) w = nullptr;
+        return e;
     }
-    hipError_t run_word(hipStream_t st, uint32_t** out) {
-        if (!run) {
-            hipError_t e = hipMalloc((void**)&run, sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(run, 0, sizeof(uint32_t), st);
-            if (e != hipSuccess) {
-                run = nullptr;
-                return e;
-            }
-        }
-        *out = run;
-        return hipSuccess;
-    }
-    hipError_t uni_word(hipStream_t st, uint32_t** out) {
-        if (!uni) {
-            hipError_t e = hipMalloc((void**)&uni, sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(uni, 0, sizeof(uint32_t), st);
-            if (e != hipSuccess) {
-                uni = nullptr;
-                return e;
-            }
-        }
-        *out = uni;
-        return hipSuccess;
-    }
-    hipError_t flag(hipStream_t st, uint32_t** out) {
-        if (!err) {
-            hipError_t e = hipMalloc((void**)&err, sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(err, 0, sizeof(uint32_t), st);
-            if (e == hipSuccess && !h_err) e = hipHostMalloc((void**)&h_err, sizeof(uint32_t), hipHostMallocDefault);
-            if (e != hipSuccess) {
-                err = nullptr;
-                return e;
-            }
-        }
-        *out = err;
-        return hipSuccess;
+    hipError_t flag(hipStream_t st) {  // err, with its pinned landing word
+        if (err) return hipSuccess;
+        hipError_t e = word(err, st);
+        if (e == hipSuccess && !h_err) e = hipHostMalloc((void**)&h_err, sizeof(uint32_t), hipHostMallocDefault);
+        if (e != hipSuccess) err = nullptr;
+        return e;
     }
     // Returns slot `which` with at least `bytes` bytes, stream-ordered on `st`.
     hipError_t get(int which, size_t bytes, hipStream_t st, uint8_t** out) {
@@ -324,6 +292,16 @@ int enter(hipStream_t st, DeviceScope& scope, DeviceState** out) {
     return BKD_OK;
 }
 
+// A C-ABI call on `stream`: the stream's device made current until the call returns, that device's
+// state, and what enter() answered.
+struct Call {
+    DeviceScope scope;
+    DeviceState* ds = nullptr;
+    const hipStream_t st;
+    int rc;
+    explicit Call(void* stream) : st((hipStream_t)stream), rc(enter(st, scope, &ds)) {}
+};
+
 // The stream's scratch, or nullptr when nothing was ever enqueued on it (no entry is created).
 StreamScratch* scratch_find(DeviceState& ds, hipStream_t st) {
     std::shared_lock<std::shared_mutex> rd(ds.maps_mu);
@@ -338,6 +316,19 @@ StreamScratch& scratch_for(DeviceState& ds, hipStream_t st) {
     if (!slot) slot.reset(new StreamScratch());
     return *slot;
 }
+
+// *err = the stream's bounds flag (StreamScratch::err), made on first use.
+int bounds_flag(DeviceState& ds, hipStream_t st, uint32_t** err) {
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);
+    const hipError_t e = sc.flag(st);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("bounds flag: ") + hipGetErrorString(e));
+    *err = sc.err;
+    return BKD_OK;
+}
+
+// What bkd_stream_sync and bkd_stream_release report for a raised bounds flag.
+constexpr const char* kBoundsMsg = "an indexed entry exceeded its base buffer (entries skipped, out = 0)";
 
 // Lanes per entry group for the direct kernel, from the size sweep (profiles/r01_size_sweep.log):
 // 4 lanes below 512 B, 8 up to 32 KiB, 32 above; then more lanes while the batch would not give
@@ -361,55 +352,43 @@ int auto_lanes(uint64_t mean_len, uint64_t n = UINT64_MAX, int cus = 256) {
 constexpr int kPF = BKD_PF;
 constexpr bool kNT = BKD_NT != 0;
 
-template <int G, class Src>
-int launch_groups(DeviceState& ds, int algo, const uint8_t* base, const Src& src, uint64_t host_count,
-                  hipStream_t stream, uint32_t* err) {
-    if (host_count == 0) return BKD_OK;
-    const uint64_t groups_per_block = bkd::kBlock / G;
-    uint64_t blocks = (host_count + groups_per_block - 1) / groups_per_block;
-    blocks = std::min<uint64_t>(blocks, (uint64_t)ds.cus);
-    const uint32_t* tab = ds.tables[algo][lane_index(G)];
-    hipLaunchKernelGGL((bkd::crc_groups_kernel<G, kPF, kNT, Src>), dim3((unsigned)blocks), dim3(bkd::kBlock), 0,
-                       stream, base, src, tab, err, g_fold_sched.load());
-    BKD_HIP(hipGetLastError());
-    return BKD_OK;
+// Turns a runtime lane count into a template argument: f(std::integral_constant<int, G>{}) for G in
+// {1 (only if MinG <= 1), 4, 8, 16, 32, 64}. The one-entry-per-group kernel exists from G = 1; the
+// plan, fused-verify and fused-package kernels from 4.
+template <int MinG, class F>
+int with_lanes(int lanes, F&& f) {
+    switch (lanes) {
+        case 1:
+            if constexpr (MinG <= 1) return f(std::integral_constant<int, 1>{});
+            break;
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+    }
+    return fail(BKD_ERR_INVALID_ARG, "lanes must be 1, 4, 8, 16, 32 or 64");
+}
+
+// Grid of the one-entry-per-group kernels: a block per kBlock / G entries, at most one per CU.
+unsigned group_blocks(const DeviceState& ds, uint64_t n, int G) {
+    const uint64_t per_block = bkd::kBlock / G;
+    return (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)ds.cus);
 }
 
 // host_count: an upper bound of src.count() used only to size the grid.
 template <class Src>
 int dispatch_lanes(DeviceState& ds, int lanes, int algo, const uint8_t* base, const Src& src, uint64_t host_count,
                    hipStream_t stream, uint32_t* err = nullptr) {
-    switch (lanes) {
-        case 1: return launch_groups<1>(ds, algo, base, src, host_count, stream, err);
-        case 4: return launch_groups<4>(ds, algo, base, src, host_count, stream, err);
-        case 8: return launch_groups<8>(ds, algo, base, src, host_count, stream, err);
-        case 16: return launch_groups<16>(ds, algo, base, src, host_count, stream, err);
-        case 32: return launch_groups<32>(ds, algo, base, src, host_count, stream, err);
-        case 64: return launch_groups<64>(ds, algo, base, src, host_count, stream, err);
-        default: return fail(BKD_ERR_INVALID_ARG, "lanes must be 1, 4, 8, 16, 32 or 64");
-    }
-}
-
-template <int G>
-void launch_plan_chunks(const bkd::PlanRun& run, const uint8_t* base, const bkd::PlanDesc* descs, bool d8,
-                        uint32_t r0h, const uint32_t* count, const uint32_t* tab,
-                        uint32_t* out, uint32_t* partials, const bkd::PlanDirectSrc& ov, int blocks, hipStream_t st,
-                        uint32_t* err, int pf) {
-    // pf: read once by launch_plan (one value per call); d8 (PlanDesc8) only with the default pf
-    if (pf == 8)
-        hipLaunchKernelGGL((bkd::crc_plan_chunks_kernel<G, 8, kNT, bkd::PlanDirectSrc>), dim3((unsigned)blocks),
-                           dim3(bkd::kBlock), 0, st, base, descs, r0h, count, tab, out, partials, ov, run, err);
-    else if (pf == 4)
-        hipLaunchKernelGGL((bkd::crc_plan_chunks_kernel<G, 4, kNT, bkd::PlanDirectSrc>), dim3((unsigned)blocks),
-                           dim3(bkd::kBlock), 0, st, base, descs, r0h, count, tab, out, partials, ov, run, err);
-    else if (d8)
-        hipLaunchKernelGGL((bkd::crc_plan_chunks_kernel<G, 2, kNT, bkd::PlanDirectSrc, bkd::PlanDesc8>),
-                           dim3((unsigned)blocks), dim3(bkd::kBlock), 0, st, base,
-                           reinterpret_cast<const bkd::PlanDesc8*>(descs), r0h, count, tab, out, partials, ov, run,
-                           err);
-    else
-        hipLaunchKernelGGL((bkd::crc_plan_chunks_kernel<G, 2, kNT, bkd::PlanDirectSrc>), dim3((unsigned)blocks),
-                           dim3(bkd::kBlock), 0, st, base, descs, r0h, count, tab, out, partials, ov, run, err);
+    return with_lanes<1>(lanes, [&](auto g) -> int {
+        constexpr int G = decltype(g)::value;
+        if (host_count == 0) return BKD_OK;
+        hipLaunchKernelGGL((bkd::crc_groups_kernel<G, kPF, kNT, Src>), dim3(group_blocks(ds, host_count, G)),
+                           dim3(bkd::kBlock), 0, stream, base, src, ds.tables[algo][lane_index(G)], err,
+                           g_fold_sched.load());
+        BKD_HIP(hipGetLastError());
+        return BKD_OK;
+    });
 }
 
 // Indexed batch through the chunked plan (plan_kernels.hpp): five stream-ordered kernels, no
@@ -465,19 +444,17 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
     StreamScratch& sc = scratch_for(ds, st);
     std::lock_guard<std::recursive_mutex> lk(sc.mu);
     uint8_t* sb = nullptr;
-    uint32_t* err = nullptr;
-    uint32_t* run_word = nullptr;
-    uint32_t* uni = nullptr;
     // without a short class (mean entry > 1 KiB), lengths all within 1/16 + 64 B of the first
     // entry's skip the chunks: the chunk kernel computes them whole, as the direct kernel would (PlanRun::uniform,
     // decided on the device: plan_count's per-block ballots, reduced by plan_scan). Only where the
     // direct kernel would use the plan's lane count.
     const bool gate = pg.small == 0u && direct_gate && auto_lanes(size / n, n, ds.cus) == G;
     hipError_t e = sc.get(0, cv.used, st, &sb);
-    if (e == hipSuccess) e = sc.flag(st, &err);
-    if (e == hipSuccess && pg.small) e = sc.run_word(st, &run_word);
-    if (e == hipSuccess && gate) e = sc.uni_word(st, &uni);
+    if (e == hipSuccess) e = sc.flag(st);
+    if (e == hipSuccess && pg.small) e = sc.word(sc.run, st);
+    if (e == hipSuccess && gate) e = sc.word(sc.uni, st);
     if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("plan scratch: ") + hipGetErrorString(e));
+    uint32_t *err = sc.err, *run_word = pg.small ? sc.run : nullptr, *uni = gate ? sc.uni : nullptr;
     if (++sc.epoch == 0u) ++sc.epoch;  // 0 is the words' initial value
     const bkd::PlanRun run = ext_flag ? bkd::PlanRun{ext_flag, nullptr, ext_epoch} : bkd::PlanRun{run_word, uni, sc.epoch};
     uint32_t *blk = Carver::at<uint32_t>(sb, o_blk), *blive = Carver::at<uint32_t>(sb, o_live),
@@ -488,17 +465,15 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
     bkd::PlanDesc* descs = Carver::at<bkd::PlanDesc>(sb, o_desc);
     if (pg.small) {  // the short-entry class, in its own launch (any order against the plan kernels)
         const bkd::SmallIndexedSrc ss{n, offsets, lengths, seeds, seed_all, size, out, pg.small, run_word, run.epoch};
-        if (pg.small <= kSmallBytes4) {
-            const uint64_t per_block = bkd::kBlock / kSmallLanes;
-            const unsigned sblocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)ds.cus);
-            hipLaunchKernelGGL((bkd::crc_groups_kernel<kSmallLanes, 2, kNT, bkd::SmallIndexedSrc>), dim3(sblocks),
-                               dim3(bkd::kBlock), 0, st, base, ss, ds.tables[algo][lane_index(kSmallLanes)], err, 1);
-        } else {  // bounds above 192 B: kSmallLanesWide-lane groups (8: up to 512 B), an entry's PF + 1 steps in one register set
-            const uint64_t per_block = bkd::kBlock / kSmallLanesWide;
-            const unsigned sblocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)ds.cus);
-            hipLaunchKernelGGL((bkd::crc_groups_kernel<kSmallLanesWide, 3, kNT, bkd::SmallIndexedSrc>), dim3(sblocks),
-                               dim3(bkd::kBlock), 0, st, base, ss, ds.tables[algo][lane_index(kSmallLanesWide)], err, 1);
-        }
+        // bounds above 192 B: kSmallLanesWide-lane groups (8: up to 512 B), an entry's PF + 1 steps in one register set
+        with_lanes<4>(pg.small <= kSmallBytes4 ? kSmallLanes : kSmallLanesWide, [&](auto g) -> int {
+            constexpr int SG = decltype(g)::value;
+            if constexpr (SG == kSmallLanes || SG == kSmallLanesWide)  // the class has these two widths only
+                hipLaunchKernelGGL((bkd::crc_groups_kernel<SG, SG == kSmallLanes ? 2 : 3, kNT, bkd::SmallIndexedSrc>),
+                                   dim3(group_blocks(ds, n, SG)), dim3(bkd::kBlock), 0, st, base, ss,
+                                   ds.tables[algo][lane_index(SG)], err, 1);
+            return BKD_OK;
+        });
     }
     // count / emit / combine walk their 1024-entry blocks in grid stride (kPlanGrid blocks per CU)
     constexpr uint32_t kPlanGrid = 2;
@@ -514,13 +489,22 @@ int launch_plan(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, c
                        lengths, seeds, seed_all, size, n, pg, capacity, blkoff, pslot, hslot, hdr, descs, reps, blive, nb, run);
     const uint32_t* tab = ds.tables[algo][lane_index(G)];
     const bkd::PlanDirectSrc ov{n, offsets, lengths, seeds, seed_all, size, out, pslot, hdr, capacity, false};
-    switch (G) {
-        case 4: launch_plan_chunks<4>(run, base, descs, pg.d8 != 0u, ~seed_all, hdr + bkd::kHdrWork, tab, out, partials, ov, ds.cus, st, err, pf); break;
-        case 8: launch_plan_chunks<8>(run, base, descs, pg.d8 != 0u, ~seed_all, hdr + bkd::kHdrWork, tab, out, partials, ov, ds.cus, st, err, pf); break;
-        case 16: launch_plan_chunks<16>(run, base, descs, pg.d8 != 0u, ~seed_all, hdr + bkd::kHdrWork, tab, out, partials, ov, ds.cus, st, err, pf); break;
-        case 32: launch_plan_chunks<32>(run, base, descs, pg.d8 != 0u, ~seed_all, hdr + bkd::kHdrWork, tab, out, partials, ov, ds.cus, st, err, pf); break;
-        default: launch_plan_chunks<64>(run, base, descs, pg.d8 != 0u, ~seed_all, hdr + bkd::kHdrWork, tab, out, partials, ov, ds.cus, st, err, pf); break;
-    }
+    rc = with_lanes<4>(G, [&](auto g) -> int {
+        auto launch = [&](auto depth, const auto* d) {
+            using Desc = std::remove_cv_t<std::remove_pointer_t<decltype(d)>>;
+            hipLaunchKernelGGL((bkd::crc_plan_chunks_kernel<decltype(g)::value, decltype(depth)::value, kNT,
+                                                            bkd::PlanDirectSrc, Desc>),
+                               dim3((unsigned)ds.cus), dim3(bkd::kBlock), 0, st, base, d, ~seed_all,
+                               hdr + bkd::kHdrWork, tab, out, partials, ov, run, err);
+        };
+        // pf: read once above (one value per call); d8 (PlanDesc8) only with the default pf
+        if (pf == 8) launch(std::integral_constant<int, 8>{}, descs);
+        else if (pf == 4) launch(std::integral_constant<int, 4>{}, descs);
+        else if (pg.d8) launch(std::integral_constant<int, 2>{}, reinterpret_cast<const bkd::PlanDesc8*>(descs));
+        else launch(std::integral_constant<int, 2>{}, descs);
+        return BKD_OK;
+    });
+    if (rc) return rc;
     const uint32_t* btab = tab + bkd::gf2::byte_table_offset(G);
     hipLaunchKernelGGL(bkd::plan_combine_kernel, dim3(std::min(nb * reps, pgrid)), dim3(1024), 0, st, base, offsets, lengths, seeds,
                        seed_all, size, n, pg, xtab, btab, ds.xinv[algo],
@@ -541,33 +525,32 @@ bool indexed_direct(uint64_t size) {
 // (0 direct, 1 plan) so that a route chosen once per call cannot change under bkd_set_plan_mode.
 int indexed_batch(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, const uint64_t* offsets,
                   const uint32_t* lengths, uint64_t n, const uint32_t* seeds, uint32_t seed_all, uint32_t* out,
-                  hipStream_t st, const uint32_t* ext_flag, uint32_t ext_epoch, int route) {
+                  hipStream_t st, const uint32_t* ext_flag = nullptr, uint32_t ext_epoch = 0, int route = -1) {
     if (route < 0) route = indexed_direct(size) ? 0 : 1;
     if (route == 1)
         return launch_plan(ds, algo, base, size, offsets, lengths, n, seeds, seed_all, out, st, true, true, ext_flag,
                            ext_epoch);
     uint32_t* err = nullptr;
-    {
-        StreamScratch& sc = scratch_for(ds, st);
-        std::lock_guard<std::recursive_mutex> lk(sc.mu);
-        const hipError_t e = sc.flag(st, &err);
-        if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("bounds flag: ") + hipGetErrorString(e));
-    }
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
     bkd::IndexedSrc src{n, offsets, lengths, seeds, seed_all, size, out};
     return dispatch_lanes(ds, auto_lanes(n ? size / n : 0, n, ds.cus), algo, base, src, n, st, err);
 }
 
 bool valid_algo(int algo) { return algo == BKD_CRC32C || algo == BKD_CRC32; }
 
-// Whether p is device memory; *dev (if given) = the device it lives on.
-bool is_device_pointer(const void* p, int* dev = nullptr) {
+using bkd::host::mac_len;
+
+// The runtime's memory type of p (hipMemoryTypeUnregistered for plain pageable memory, which it does
+// not know); *dev (if given) = the device a device pointer lives on.
+hipMemoryType pointer_type(const void* p, int* dev = nullptr) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
         (void)hipGetLastError();
-        return false;
+        return hipMemoryTypeUnregistered;
     }
     if (dev) *dev = attr.device;
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+    return attr.type;
 }
 
 // ---- host-memory batches: pinned, double-buffered H2D -> kernel -> D2H -------------------
@@ -579,16 +562,11 @@ struct HostStage {
     static constexpr size_t kSeg = 64u << 20;
     static constexpr size_t kSegEntries = 1u << 20;
     bool ready = false;
-    uint8_t* h_pin[2] = {};
-    uint8_t* d_buf[2] = {};
-    uint64_t* h_off[2] = {};
-    uint32_t* h_len[2] = {};
-    uint32_t* h_seed[2] = {};
-    uint32_t* h_res[2] = {};
-    uint64_t* d_off[2] = {};
-    uint32_t* d_len[2] = {};
-    uint32_t* d_seed[2] = {};
-    uint32_t* d_res[2] = {};
+    uint8_t *h_pin[2] = {}, *d_buf[2] = {};
+    uint64_t *h_off[2] = {}, *d_off[2] = {};
+    uint32_t *h_len[2] = {}, *d_len[2] = {};
+    uint32_t *h_seed[2] = {}, *d_seed[2] = {};
+    uint32_t *h_res[2] = {}, *d_res[2] = {};
     hipStream_t st[2] = {};
     hipEvent_t done[2] = {};
     // framed-entry batches (bkd_digest_*_batch_host), allocated on first use and sized per path
@@ -596,76 +574,75 @@ struct HostStage {
     // frame headers out; verify only its first_bad word
     static constexpr size_t kAux = 64u << 20;
     bool pkg_ready = false, fb_ready = false;
-    uint8_t* h_aux[2] = {};
-    uint8_t* d_aux[2] = {};
-    uint8_t* h_frm[2] = {};
-    uint8_t* d_frm[2] = {};
-    uint64_t* h_fb[2] = {};
-    uint64_t* d_fb[2] = {};
-    // (each allocation is made once: a call after a failed init completes the set, nothing leaks)
-    int init_package() {
-        if (pkg_ready) return BKD_OK;
-        for (int s = 0; s < 2; ++s) {
-            if (!h_aux[s]) BKD_HIP(hipHostMalloc((void**)&h_aux[s], kAux, hipHostMallocDefault));
-            if (!d_aux[s]) BKD_HIP(hipMalloc((void**)&d_aux[s], kAux));
-            if (!h_frm[s]) BKD_HIP(hipHostMalloc((void**)&h_frm[s], kAux, hipHostMallocDefault));
-            if (!d_frm[s]) BKD_HIP(hipMalloc((void**)&d_frm[s], kAux));
-        }
-        pkg_ready = true;
-        return BKD_OK;
-    }
-    int init_verify() {
-        if (fb_ready) return BKD_OK;
-        for (int s = 0; s < 2; ++s) {
-            if (!h_fb[s]) BKD_HIP(hipHostMalloc((void**)&h_fb[s], sizeof(uint64_t), hipHostMallocDefault));
-            if (!d_fb[s]) BKD_HIP(hipMalloc((void**)&d_fb[s], sizeof(uint64_t)));
-        }
-        fb_ready = true;
-        return BKD_OK;
-    }
+    uint8_t *h_aux[2] = {}, *d_aux[2] = {};
+    uint8_t *h_frm[2] = {}, *d_frm[2] = {};
+    uint64_t *h_fb[2] = {}, *d_fb[2] = {};
     // reframe: the new LACs in (8 B per entry); its digests come back through d_seed / h_seed
     bool lac_ready = false;
-    int64_t* h_lac[2] = {};
-    int64_t* d_lac[2] = {};
-    int init_reframe() {
-        if (lac_ready) return BKD_OK;
-        for (int s = 0; s < 2; ++s) {
-            if (!h_lac[s]) BKD_HIP(hipHostMalloc((void**)&h_lac[s], kSegEntries * 8, hipHostMallocDefault));
-            if (!d_lac[s]) BKD_HIP(hipMalloc((void**)&d_lac[s], kSegEntries * 8));
-        }
-        lac_ready = true;
+    int64_t *h_lac[2] = {}, *d_lac[2] = {};
+    // Every buffer is made by pin() (pinned host) or dev() (device), which record it for the
+    // destructor. Each allocation is made once: a call after a failed init*() completes the set,
+    // nothing leaks.
+    std::vector<void*> pinned, device;
+    template <class T>
+    int pin(T*& p, size_t bytes) {
+        if (p) return BKD_OK;
+        BKD_HIP(hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+        pinned.push_back(p);
         return BKD_OK;
     }
-    ~HostStage() {  // (bkd_host_release: idle sets only, so no work of theirs is queued)
-        for (int s = 0; s < 2; ++s) {
-            for (void* h : {(void*)h_pin[s], (void*)h_off[s], (void*)h_len[s], (void*)h_seed[s], (void*)h_res[s],
-                            (void*)h_aux[s], (void*)h_frm[s], (void*)h_fb[s], (void*)h_lac[s]})
-                if (h) (void)hipHostFree(h);
-            for (void* d : {(void*)d_buf[s], (void*)d_off[s], (void*)d_len[s], (void*)d_seed[s], (void*)d_res[s],
-                            (void*)d_aux[s], (void*)d_frm[s], (void*)d_fb[s], (void*)d_lac[s]})
-                if (d) (void)hipFree(d);
-            if (st[s]) (void)hipStreamDestroy(st[s]);
-            if (done[s]) (void)hipEventDestroy(done[s]);
-        }
+    template <class T>
+    int dev(T*& p, size_t bytes) {
+        if (p) return BKD_OK;
+        BKD_HIP(hipMalloc((void**)&p, bytes));
+        device.push_back(p);
+        return BKD_OK;
     }
     int init() {
         if (ready) return BKD_OK;
-        for (int s = 0; s < 2; ++s) {
-            if (!h_pin[s]) BKD_HIP(hipHostMalloc((void**)&h_pin[s], kSeg, hipHostMallocDefault));
-            if (!d_buf[s]) BKD_HIP(hipMalloc((void**)&d_buf[s], kSeg));
-            if (!h_off[s]) BKD_HIP(hipHostMalloc((void**)&h_off[s], kSegEntries * 8, hipHostMallocDefault));
-            if (!h_len[s]) BKD_HIP(hipHostMalloc((void**)&h_len[s], kSegEntries * 4, hipHostMallocDefault));
-            if (!h_seed[s]) BKD_HIP(hipHostMalloc((void**)&h_seed[s], kSegEntries * 4, hipHostMallocDefault));
-            if (!h_res[s]) BKD_HIP(hipHostMalloc((void**)&h_res[s], kSegEntries * 4, hipHostMallocDefault));
-            if (!d_off[s]) BKD_HIP(hipMalloc((void**)&d_off[s], kSegEntries * 8));
-            if (!d_len[s]) BKD_HIP(hipMalloc((void**)&d_len[s], kSegEntries * 4));
-            if (!d_seed[s]) BKD_HIP(hipMalloc((void**)&d_seed[s], kSegEntries * 4));
-            if (!d_res[s]) BKD_HIP(hipMalloc((void**)&d_res[s], kSegEntries * 4));
+        for (int s = 0, rc; s < 2; ++s) {
+            if ((rc = pin(h_pin[s], kSeg)) || (rc = dev(d_buf[s], kSeg)) ||
+                (rc = pin(h_off[s], kSegEntries * 8)) || (rc = dev(d_off[s], kSegEntries * 8)) ||
+                (rc = pin(h_len[s], kSegEntries * 4)) || (rc = dev(d_len[s], kSegEntries * 4)) ||
+                (rc = pin(h_seed[s], kSegEntries * 4)) || (rc = dev(d_seed[s], kSegEntries * 4)) ||
+                (rc = pin(h_res[s], kSegEntries * 4)) || (rc = dev(d_res[s], kSegEntries * 4)))
+                return rc;
             if (!st[s]) BKD_HIP(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
             if (!done[s]) BKD_HIP(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
         }
         ready = true;
         return BKD_OK;
+    }
+    int init_package() {
+        if (pkg_ready) return BKD_OK;
+        for (int s = 0, rc; s < 2; ++s)
+            if ((rc = pin(h_aux[s], kAux)) || (rc = dev(d_aux[s], kAux)) || (rc = pin(h_frm[s], kAux)) ||
+                (rc = dev(d_frm[s], kAux)))
+                return rc;
+        pkg_ready = true;
+        return BKD_OK;
+    }
+    int init_verify() {
+        if (fb_ready) return BKD_OK;
+        for (int s = 0, rc; s < 2; ++s)
+            if ((rc = pin(h_fb[s], sizeof(uint64_t))) || (rc = dev(d_fb[s], sizeof(uint64_t)))) return rc;
+        fb_ready = true;
+        return BKD_OK;
+    }
+    int init_reframe() {
+        if (lac_ready) return BKD_OK;
+        for (int s = 0, rc; s < 2; ++s)
+            if ((rc = pin(h_lac[s], kSegEntries * 8)) || (rc = dev(d_lac[s], kSegEntries * 8))) return rc;
+        lac_ready = true;
+        return BKD_OK;
+    }
+    ~HostStage() {  // (bkd_host_release: idle sets only, so no work of theirs is queued)
+        for (void* h : pinned) (void)hipHostFree(h);
+        for (void* d : device) (void)hipFree(d);
+        for (int s = 0; s < 2; ++s) {
+            if (st[s]) (void)hipStreamDestroy(st[s]);
+            if (done[s]) (void)hipEventDestroy(done[s]);
+        }
     }
 };
 
@@ -718,6 +695,19 @@ class StageLease {
   private:
     StagePool& pool_;
     HostStage* hs_ = nullptr;
+};
+
+// A host-resident call on the GPU route: entered on the null stream, with a staging set leased for
+// the call and its init() and the named init_*() groups run. rc: the first failure of any of these.
+struct StagedCall : Call {
+    std::optional<StageLease> lease;
+    template <class... Init>
+    explicit StagedCall(Init... more) : Call(nullptr) {
+        if (rc) return;
+        lease.emplace((int)(ds - g_dev));
+        rc = (**lease).init();
+        ((rc = rc ? rc : ((**lease).*more)()), ...);
+    }
 };
 
 // Host copies into pinned staging (a pageable source, or a list of separate entry buffers such as a
@@ -773,19 +763,6 @@ void gather_entries(const void* const* src, const uint32_t* len, uint64_t cnt, u
     });
 }
 
-int indexed_batch(DeviceState& ds, int algo, const uint8_t* base, uint64_t size, const uint64_t* offsets,
-                  const uint32_t* lengths, uint64_t n, const uint32_t* seeds, uint32_t seed_all, uint32_t* out,
-                  hipStream_t st, const uint32_t* ext_flag = nullptr, uint32_t ext_epoch = 0, int route = -1);
-
-bool is_pinned_host(const void* p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeHost;
-}
-
 // Unsorted index: one device copy of the spanned bytes. The buffers are allocated with hipMalloc
 // and released with hipFree: reusing stream-ordered (hipMallocAsync) allocations of this size for
 // the copy gave wrong digests from the second call on (128-512 MiB spans, both pinned and pageable
@@ -823,23 +800,54 @@ int host_batch_oneshot(DeviceState& ds, HostStage& hs, int algo, const uint8_t* 
     return rc;
 }
 
+// The two-slot loop of every staged route. cut(i0, &bytes) returns the end of the segment that
+// starts at entry i0 and its staged bytes; seg(s, i0, cnt, bytes) enqueues it on slot s = k % 2
+// (copies in, the device sequence, copies out) and drain_slot(s, i0, cnt) hands a finished slot's
+// results back, so one segment's gather and H2D overlap the other's kernels and D2H.
+template <class Cut, class Seg, class Drain>
+int staged_pipeline(HostStage& hs, uint64_t n, Cut&& cut, Seg&& seg, Drain&& drain_slot) {
+    uint64_t pend_i0[2] = {0, 0}, pend_cnt[2] = {0, 0};
+    bool busy[2] = {false, false};
+    auto drain = [&](int s) -> int {  // wait for slot s and hand its results back
+        if (!busy[s]) return BKD_OK;
+        BKD_HIP(hipEventSynchronize(hs.done[s]));
+        busy[s] = false;
+        return drain_slot(s, pend_i0[s], pend_cnt[s]);
+    };
+    int rc = BKD_OK;
+    uint64_t i0 = 0;
+    for (int k = 0; i0 < n && rc == BKD_OK; ++k) {
+        const int s = k & 1;
+        uint64_t bytes = 0;
+        const uint64_t i1 = cut(i0, &bytes);
+        if ((rc = drain(s))) break;
+        if ((rc = seg(s, i0, i1 - i0, bytes))) {
+            (void)hipStreamSynchronize(hs.st[s]);  // copies of the failed segment may be queued
+            break;
+        }
+        // every exit below goes through the final drains: no staging set returns to the pool with
+        // copies or kernels of this call still queued on its streams
+        const hipError_t e = hipEventRecord(hs.done[s], hs.st[s]);
+        if (e != hipSuccess) {
+            rc = fail(BKD_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+            (void)hipStreamSynchronize(hs.st[s]);
+            break;
+        }
+        busy[s] = true;
+        pend_i0[s] = i0;
+        pend_cnt[s] = i1 - i0;
+        i0 = i1;
+    }
+    const int r0 = drain(0), r1 = drain(1);
+    return rc ? rc : (r0 ? r0 : r1);
+}
+
+// The contiguous route: segments cut by the span of the sorted offsets.
 int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t* h_base, const uint64_t* h_offsets,
                          const uint32_t* h_lengths, uint64_t n, const uint32_t* h_seeds, uint32_t seed_all,
                          uint32_t* h_out) {
-    const bool pinned = is_pinned_host(h_base);
-    uint64_t pend_i0[2] = {0, 0}, pend_cnt[2] = {0, 0};
-    bool busy[2] = {false, false};
-    auto drain = [&](int s) -> int {  // wait for slot s and hand its digests back
-        if (!busy[s]) return BKD_OK;
-        BKD_HIP(hipEventSynchronize(hs.done[s]));
-        memcpy(h_out + pend_i0[s], hs.h_res[s], pend_cnt[s] * 4);
-        busy[s] = false;
-        return BKD_OK;
-    };
-    uint64_t i0 = 0;
-    int rc = BKD_OK;
-    for (int k = 0; i0 < n && rc == BKD_OK; ++k) {
-        const int s = k & 1;
+    const bool pinned = pointer_type(h_base) == hipMemoryTypeHost;
+    auto cut = [&](uint64_t i0, uint64_t* span) {
         const uint64_t b0 = h_offsets[i0];
         uint64_t i1 = i0, b1 = b0;
         while (i1 < n && i1 - i0 < HostStage::kSegEntries) {
@@ -848,8 +856,11 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
             b1 = e1;
             ++i1;
         }
-        const uint64_t cnt = i1 - i0, span = b1 - b0;  // span <= kSeg: longer entries arrive in pieces
-        if ((rc = drain(s))) break;
+        *span = b1 - b0;  // <= kSeg: longer entries arrive in pieces
+        return i1;
+    };
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t span) -> int {
+        const uint64_t b0 = h_offsets[i0];
         for (uint64_t j = 0; j < cnt; ++j) {
             hs.h_off[s][j] = h_offsets[i0 + j] - b0;
             hs.h_len[s][j] = h_lengths[i0 + j];
@@ -865,65 +876,42 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
         if (e == hipSuccess) e = hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(hs.d_len[s], hs.h_len[s], cnt * 4, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && h_seeds) e = hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            rc = fail(BKD_ERR_HIP, std::string("host batch H2D: ") + hipGetErrorString(e));
-            break;
-        }
-        rc = indexed_batch(ds, algo, hs.d_buf[s], span, hs.d_off[s], hs.d_len[s], cnt, h_seeds ? hs.d_seed[s] : nullptr,
-                           seed_all, hs.d_res[s], st);
-        if (rc) break;
+        if (e != hipSuccess) return fail(BKD_ERR_HIP, std::string("host batch H2D: ") + hipGetErrorString(e));
+        const int rc = indexed_batch(ds, algo, hs.d_buf[s], span, hs.d_off[s], hs.d_len[s], cnt,
+                                     h_seeds ? hs.d_seed[s] : nullptr, seed_all, hs.d_res[s], st);
+        if (rc) return rc;
         e = hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(hs.done[s], st);
-        if (e != hipSuccess) {
-            rc = fail(BKD_ERR_HIP, std::string("host batch D2H: ") + hipGetErrorString(e));
-            break;
-        }
-        busy[s] = true;
-        pend_i0[s] = i0;
-        pend_cnt[s] = cnt;
-        i0 = i1;
-    }
-    const int r0 = drain(0), r1 = drain(1);
-    return rc ? rc : (r0 ? r0 : r1);
+        if (e != hipSuccess) return fail(BKD_ERR_HIP, std::string("host batch D2H: ") + hipGetErrorString(e));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {  // hand the slot's digests back
+        memcpy(h_out + i0, hs.h_res[s], cnt * 4);
+        return BKD_OK;
+    };
+    return staged_pipeline(hs, n, cut, seg, drain);
 }
 
 // ---- DigestManager batch framing: the device sequences shared by the device- and host-resident
 // entry points -------------------------------------------------------------------------------
 
-// Package, fused route (4..64-lane groups, frames apart from the payload): each lane group
-// builds its entry's header from the index arrays and folds header + payload in one pass, storing the
-// digest (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
-template <int G>
-void launch_package_fused(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_entry_ids,
-                          const int64_t* d_lacs, const int64_t* d_length_fields, const uint8_t* payload,
-                          uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
-                          uint32_t* d_digests, uint32_t* err) {
-    const uint64_t per_block = bkd::kBlock / G;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)ds.cus);
-    hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT>), dim3(blocks), dim3(bkd::kBlock), 0, st, payload,
-                       payload_size, d_offsets, d_lengths, n, ledger_id, d_entry_ids, d_lacs, d_length_fields,
-                       ds.tables[algo][lane_index(G)], d_digests, err, g_fold_sched.load());
-}
-
 // Package: header kernel (32 B BE header, header CRC as the payload's seed) -> payload CRCs through
 // the direct kernel -> digest kernel (BE digest after the header, in a pass of its own: the payload
 // groups storing it themselves measured 3 % slower on 1M x 4 KiB, profiles/r03m_ab_order*.log) — or
-// the fused route above, which folds the header inside the payload kernel. Out-of-range payload
+// the fused route, which folds the header inside the payload kernel. Out-of-range payload
 // entries raise the stream's bounds flag.
+// Fused route (4..64-lane groups, frames apart from the payload): each lane group builds its
+// entry's header from the index arrays and folds header + payload in one pass, storing the digest
+// (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
 int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_entry_ids,
                    const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
                    uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
                    void* d_frames, uint64_t frame_stride, uint32_t* d_digests) {
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     const int lanes = auto_lanes(payload_size / n, n, ds.cus);
     const uint32_t* tab = ds.tables[algo][lane_index(lanes)];
     uint32_t* err = nullptr;
-    {
-        StreamScratch& sc = scratch_for(ds, st);
-        std::lock_guard<std::recursive_mutex> lk(sc.mu);
-        const hipError_t e = sc.flag(st, &err);
-        if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("bounds flag: ") + hipGetErrorString(e));
-    }
+    int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     // The fused route when the frames are their own buffer (DigestManager's ByteBufList(header, data),
     // bench.py --config verify4k: 0.674 -> 0.659 ms per 1M 4 KiB entries); frames written in place in
@@ -932,15 +920,16 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     const uint64_t pl0 = (uint64_t)(uintptr_t)d_payload, pl1 = pl0 + payload_size;
     const bool frames_apart = fr1 <= pl0 || pl1 <= fr0;
     if (lanes >= 4 && frames_apart) {
-        const uint8_t* pl = (const uint8_t*)d_payload;
-        switch (lanes) {
-            case 4: launch_package_fused<4>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
-            case 8: launch_package_fused<8>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
-            case 16: launch_package_fused<16>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
-            case 32: launch_package_fused<32>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
-            default: launch_package_fused<64>(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, pl, payload_size, d_offsets, d_lengths, n, d_digests, err); break;
-        }
-        BKD_HIP(hipGetLastError());
+        rc = with_lanes<4>(lanes, [&](auto g) -> int {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                               dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths, n,
+                               ledger_id, d_entry_ids, d_lacs, d_length_fields, ds.tables[algo][lane_index(G)],
+                               d_digests, err, g_fold_sched.load());
+            BKD_HIP(hipGetLastError());
+            return BKD_OK;
+        });
+        if (rc) return rc;
         hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
                            d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
         BKD_HIP(hipGetLastError());
@@ -951,25 +940,12 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
                        d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
     BKD_HIP(hipGetLastError());
     bkd::IndexedSrc src{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests};
-    int rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
+    rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
     if (rc) return rc;
     hipLaunchKernelGGL(bkd::package_digest_kernel, dim3(blocks), dim3(256), 0, st, d_digests, n,
                        (uint8_t*)d_frames, frame_stride, mac);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
-}
-
-// Fused verify of near-uniform frames: one kernel per lane count (crc_verify_fused_kernel).
-template <int G>
-void launch_verify_fused(DeviceState& ds, hipStream_t st, int algo, const uint8_t* framed, uint64_t size,
-                         const uint64_t* offsets, const uint32_t* lengths, uint64_t n, uint32_t mac, int64_t ledger_id,
-                         int64_t first_entry_id, int id_checks, int32_t* status, uint64_t* first_bad,
-                         const uint32_t* vflag, uint32_t vepoch) {
-    const uint64_t per_block = bkd::kBlock / G;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)ds.cus);
-    hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT>), dim3(blocks), dim3(bkd::kBlock), 0, st, framed, size,
-                       offsets, lengths, n, mac, ledger_id, first_entry_id, id_checks, ds.tables[algo][lane_index(G)],
-                       status, (unsigned long long*)first_bad, vflag, vepoch, g_fold_sched.load());
 }
 
 // Verify (bkd_digest_verify_batch and bkd_entrylog_verify): header CRCs -> payload CRCs seeded
@@ -981,7 +957,7 @@ void launch_verify_fused(DeviceState& ds, hipStream_t st, int algo, const uint8_
 int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, int64_t first_entry_id,
                   int id_checks, const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
                   const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad) {
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     if (n == 0) {
         BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
         return BKD_OK;
@@ -1013,29 +989,26 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
     uint32_t* vflag = nullptr;
     uint32_t vepoch = 0;
     if (fused) {
-        e = sc.vflag_word(st, &vflag);
+        e = sc.word(sc.vflag, st);
         if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("verify gate: ") + hipGetErrorString(e));
+        vflag = sc.vflag;
         if (++sc.vepoch == 0u) ++sc.vepoch;  // 0 is the word's initial value
         vepoch = sc.vepoch;
         const unsigned gblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, (uint64_t)ds.cus);
         hipLaunchKernelGGL(bkd::verify_gate_kernel, dim3(gblocks), dim3(1024), 0, st, d_lengths, n, d_first_bad, vflag,
                            vepoch);
-        const uint8_t* fb = (const uint8_t*)d_framed;
-        switch (fused_lanes) {
-            case 1:  // (a forced one-lane geometry: the fused kernel's narrowest group)
-            case 4: launch_verify_fused<4>(ds, st, algo, fb, framed_size, d_offsets, d_lengths, n, mac, ledger_id,
-                                           first_entry_id, id_checks, d_status, d_first_bad, vflag, vepoch); break;
-            case 8: launch_verify_fused<8>(ds, st, algo, fb, framed_size, d_offsets, d_lengths, n, mac, ledger_id,
-                                           first_entry_id, id_checks, d_status, d_first_bad, vflag, vepoch); break;
-            case 16: launch_verify_fused<16>(ds, st, algo, fb, framed_size, d_offsets, d_lengths, n, mac, ledger_id,
-                                             first_entry_id, id_checks, d_status, d_first_bad, vflag, vepoch); break;
-            case 32: launch_verify_fused<32>(ds, st, algo, fb, framed_size, d_offsets, d_lengths, n, mac, ledger_id,
-                                             first_entry_id, id_checks, d_status, d_first_bad, vflag, vepoch); break;
-            default: launch_verify_fused<64>(ds, st, algo, fb, framed_size, d_offsets, d_lengths, n, mac, ledger_id,
-                                             first_entry_id, id_checks, d_status, d_first_bad, vflag, vepoch); break;
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
+        // one kernel per lane count (crc_verify_fused_kernel); a forced one-lane geometry takes its
+        // narrowest group, 4
+        const int rc = with_lanes<4>(fused_lanes == 1 ? 4 : fused_lanes, [&](auto g) -> int {
+            constexpr int G = decltype(g)::value;
+            hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                               dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
+                               mac, ledger_id, first_entry_id, id_checks, ds.tables[algo][lane_index(G)], d_status,
+                               (unsigned long long*)d_first_bad, vflag, vepoch, g_fold_sched.load());
+            const hipError_t le = hipGetLastError();
+            return le == hipSuccess ? BKD_OK : fail(BKD_ERR_HIP, hipGetErrorString(le));
+        });
+        if (rc) return rc;
     }
     const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
     hipLaunchKernelGGL(bkd::verify_header_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab, (const uint8_t*)d_framed,
@@ -1062,7 +1035,7 @@ int reframe_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
                    int id_checks, bool trusted, void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
                    const uint32_t* d_lengths, uint64_t n, const int64_t* d_new_lacs, void* d_out_frames,
                    uint64_t frame_stride, uint32_t* d_digests, int32_t* d_status, uint64_t* d_first_bad) {
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     if (n == 0) {
         BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
         return BKD_OK;
@@ -1080,16 +1053,10 @@ int reframe_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     const uint32_t* x32tab = ds.tables[algo][lane_index(4)] + 1024;  // x^32 operator, 4 x 256
     const uint64_t ntiles = (n + bkd::kReframeBlock - 1) / bkd::kReframeBlock;
     const unsigned blocks = (unsigned)std::min<uint64_t>(ntiles, 8u * (uint64_t)ds.cus);
-    if (trusted)
-        hipLaunchKernelGGL(bkd::reframe_frame_kernel<true>, dim3(blocks), dim3(bkd::kReframeBlock), 0, st, x32tab,
-                           ds.xp8[algo], bkd::gf2::poly(algo), (uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
-                           mac, d_new_lacs, ledger_id, first_entry_id, id_checks, (uint8_t*)d_out_frames, frame_stride,
-                           d_digests, d_status, (unsigned long long*)d_first_bad);
-    else
-        hipLaunchKernelGGL(bkd::reframe_frame_kernel<false>, dim3(blocks), dim3(bkd::kReframeBlock), 0, st, x32tab,
-                           ds.xp8[algo], bkd::gf2::poly(algo), (uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
-                           mac, d_new_lacs, ledger_id, first_entry_id, id_checks, (uint8_t*)d_out_frames, frame_stride,
-                           d_digests, d_status, (unsigned long long*)d_first_bad);
+    hipLaunchKernelGGL(trusted ? bkd::reframe_frame_kernel<true> : bkd::reframe_frame_kernel<false>, dim3(blocks),
+                       dim3(bkd::kReframeBlock), 0, st, x32tab, ds.xp8[algo], bkd::gf2::poly(algo), (uint8_t*)d_framed,
+                       framed_size, d_offsets, d_lengths, n, mac, d_new_lacs, ledger_id, first_entry_id, id_checks,
+                       (uint8_t*)d_out_frames, frame_stride, d_digests, d_status, (unsigned long long*)d_first_bad);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
 }
@@ -1102,45 +1069,34 @@ int reframe_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
 template <class Seg, class Drain>
 int host_segments(HostStage& hs, const uint32_t* h_lengths, uint64_t n, uint64_t max_entries, Seg&& seg,
                   Drain&& drain_slot) {
-    uint64_t pend_i0[2] = {0, 0}, pend_cnt[2] = {0, 0};
-    bool busy[2] = {false, false};
-    auto drain = [&](int s) -> int {
-        if (!busy[s]) return BKD_OK;
-        BKD_HIP(hipEventSynchronize(hs.done[s]));
-        busy[s] = false;
-        return drain_slot(s, pend_i0[s], pend_cnt[s]);
-    };
     // every entry fits a segment, checked before any work is enqueued
     for (uint64_t i = 0; i < n; ++i)
         if (h_lengths[i] > HostStage::kSeg)
             return fail(BKD_ERR_INVALID_ARG, "host entry " + std::to_string(i) + " is larger than 64 MiB");
-    int rc = BKD_OK;
-    uint64_t i0 = 0;
-    for (int k = 0; i0 < n && rc == BKD_OK; ++k) {
-        const int s = k & 1;
-        uint64_t i1 = i0, bytes = 0;
-        while (i1 < n && i1 - i0 < max_entries && (i1 == i0 || bytes + h_lengths[i1] <= HostStage::kSeg))
-            bytes += h_lengths[i1++];
-        if ((rc = drain(s))) break;
-        if ((rc = seg(s, i0, i1 - i0, bytes))) {
-            (void)hipStreamSynchronize(hs.st[s]);  // copies of the failed segment may be queued
-            break;
-        }
-        // every exit below goes through the final drains: no staging set returns to the pool with
-        // copies or kernels of this call still queued on its streams
-        const hipError_t e = hipEventRecord(hs.done[s], hs.st[s]);
-        if (e != hipSuccess) {
-            rc = fail(BKD_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
-            (void)hipStreamSynchronize(hs.st[s]);
-            break;
-        }
-        busy[s] = true;
-        pend_i0[s] = i0;
-        pend_cnt[s] = i1 - i0;
-        i0 = i1;
-    }
-    const int r0 = drain(0), r1 = drain(1);
-    return rc ? rc : (r0 ? r0 : r1);
+    auto cut = [&](uint64_t i0, uint64_t* bytes) {  // by summed lengths: the entries are gathered back to back
+        uint64_t i1 = i0;
+        while (i1 < n && i1 - i0 < max_entries && (i1 == i0 || *bytes + h_lengths[i1] <= HostStage::kSeg))
+            *bytes += h_lengths[i1++];
+        return i1;
+    };
+    return staged_pipeline(hs, n, cut, seg, drain_slot);
+}
+
+// A segment of separate entry buffers into slot s: gathered back to back into the pinned buffer,
+// then the bytes, where each entry landed and the lengths copied H2D on the slot's stream.
+int stage_entries(HostStage& hs, int s, const void* const* ptrs, const uint32_t* lens, uint64_t i0, uint64_t cnt,
+                  uint64_t bytes) {
+    gather_entries(ptrs + i0, lens + i0, cnt, hs.h_pin[s], hs.h_off[s]);
+    BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, hs.st[s]));
+    BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, hs.st[s]));
+    BKD_HIP(hipMemcpyAsync(hs.d_len[s], lens + i0, cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+    return BKD_OK;
+}
+
+// Folds slot s's first_bad (relative to its segment [i0, i0 + cnt)) into the call's.
+void merge_first_bad(const HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t* h_first_bad) {
+    const uint64_t fb = *hs.h_fb[s];
+    if (fb < cnt && i0 + fb < *h_first_bad) *h_first_bad = i0 + fb;
 }
 
 // ---- per-call resume (IntHash.resume) -------------------------------------------------------
@@ -1191,10 +1147,11 @@ int host_route(bool oversize = false) {
     return bkd::host::Pool::get().active() >= cpu_route_min_threads() ? 1 : 2;
 }
 
-bool any_longer(const uint32_t* lengths, uint64_t n, uint64_t limit) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (lengths[i] > limit) return true;
-    return false;
+// The framed host routes' choice (host_route): oversize when an entry is longer than a staging segment.
+int framed_host_route(const uint32_t* lengths, uint64_t n) {
+    bool oversize = false;
+    for (uint64_t i = 0; i < n && !oversize; ++i) oversize = lengths[i] > HostStage::kSeg;
+    return host_route(oversize);
 }
 
 int cpu_resume(int algo, uint32_t current, const void* p, uint64_t len, uint32_t* out) {
@@ -1240,10 +1197,10 @@ void call_release(int dev, CallScratch* c) {
 }
 
 int resume_device(int algo, uint32_t current, const void* ptr, uint64_t len, hipStream_t st, uint32_t* out) {
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
+    Call call(st);
+    int rc = call.rc;
     if (rc) return rc;
+    DeviceState* const ds = call.ds;
     const int dev = (int)(ds - g_dev);
     CallScratch* c = nullptr;
     if ((rc = call_acquire(dev, st, &c))) return rc;
@@ -1357,24 +1314,21 @@ int bkd_crc_batch_uniform(int algo, const void* d_base, uint64_t stride, uint32_
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
     if (n && (!d_base || !d_out)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (n > 1 && stride < entry_len) return fail(BKD_ERR_INVALID_ARG, "stride < entry_len");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
+    Call call(stream);
+    if (call.rc) return call.rc;
     bkd::UniformSrc src{n, stride, entry_len, d_seeds, seed_all, d_out};
     // entries of 16..48 B: one lane per entry, both loads of an entry in flight with the next
     // entry's (uniform_small_loop): 2.2x the 4-lane rate at 32 B; from 64 B on 4 lanes win
-    int lanes = auto_lanes(entry_len, n, ds->cus);
-    if (g_forced_lanes.load() == 0 && entry_len >= 16u && entry_len <= 48u && n >= (uint64_t)ds->cus * bkd::kBlock)
+    int lanes = auto_lanes(entry_len, n, call.ds->cus);
+    if (g_forced_lanes.load() == 0 && entry_len >= 16u && entry_len <= 48u && n >= (uint64_t)call.ds->cus * bkd::kBlock)
         lanes = 1;
     // 256..511 B: 8 lanes (two to four 128-byte steps; the three-set short loop up to 384 B) beat 4
     // lanes since the short loop's waits are countable: 256 B 0.934 vs 1.028 ms, 512 B 0.826 vs
     // 0.915 ms per 4 GiB (profiles/r03v_size_sweep.log); indexed batches keep auto_lanes
     if (g_forced_lanes.load() == 0 && lanes == 4 && entry_len >= 256u && entry_len < 512u) lanes = 8;
     if (lanes == 8 && entry_len >= bkd::kTailUncondSteps * 16u * 8u)  // measured at 8 lanes only
-        return dispatch_lanes(*ds, lanes, algo, (const uint8_t*)d_base, bkd::UniformLongSrc{src}, n, st);
-    return dispatch_lanes(*ds, lanes, algo, (const uint8_t*)d_base, src, n, st);
+        return dispatch_lanes(*call.ds, lanes, algo, (const uint8_t*)d_base, bkd::UniformLongSrc{src}, n, call.st);
+    return dispatch_lanes(*call.ds, lanes, algo, (const uint8_t*)d_base, src, n, call.st);
 }
 
 int bkd_crc_batch(int algo, const void* d_base, uint64_t base_size, const uint64_t* d_offsets,
@@ -1383,66 +1337,57 @@ int bkd_crc_batch(int algo, const void* d_base, uint64_t base_size, const uint64
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
     if (n && (!d_offsets || !d_lengths || !d_out)) return fail(BKD_ERR_INVALID_ARG, "null index/out");
     if (n && !d_base && base_size) return fail(BKD_ERR_INVALID_ARG, "null base");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    return indexed_batch(*ds, algo, (const uint8_t*)d_base, base_size, d_offsets, d_lengths, n, d_seeds, seed_all,
-                         d_out, st);
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return indexed_batch(*call.ds, algo, (const uint8_t*)d_base, base_size, d_offsets, d_lengths, n, d_seeds, seed_all,
+                         d_out, call.st);
 }
 
 int bkd_stream_sync(void* stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    StreamScratch* scp = scratch_find(*ds, st);  // (no entry for streams that only sync)
+    Call call(stream);
+    if (call.rc) return call.rc;
+    StreamScratch* scp = scratch_find(*call.ds, call.st);  // (no entry for streams that only sync)
     if (!scp) {
-        BKD_HIP(hipStreamSynchronize(st));
+        BKD_HIP(hipStreamSynchronize(call.st));
         return BKD_OK;
     }
     StreamScratch& sc = *scp;
     std::lock_guard<std::recursive_mutex> lk(sc.mu);
     if (!sc.err) {  // nothing indexed was ever enqueued on this stream
-        BKD_HIP(hipStreamSynchronize(st));
+        BKD_HIP(hipStreamSynchronize(call.st));
         return BKD_OK;
     }
     // read and clear this stream's flag in stream order, after the work it guards
-    BKD_HIP(hipMemcpyAsync(sc.h_err, sc.err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    BKD_HIP(hipMemsetAsync(sc.err, 0, sizeof(uint32_t), st));
-    BKD_HIP(hipStreamSynchronize(st));
-    if (*sc.h_err) return fail(BKD_ERR_BOUNDS, "an indexed entry exceeded its base buffer (entries skipped, out = 0)");
+    BKD_HIP(hipMemcpyAsync(sc.h_err, sc.err, sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    BKD_HIP(hipMemsetAsync(sc.err, 0, sizeof(uint32_t), call.st));
+    BKD_HIP(hipStreamSynchronize(call.st));
+    if (*sc.h_err) return fail(BKD_ERR_BOUNDS, kBoundsMsg);
     return BKD_OK;
 }
 
 int bkd_stream_release(void* stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
+    Call call(stream);
+    if (call.rc) return call.rc;
     std::unique_ptr<StreamScratch> sc;
     {
-        std::unique_lock<std::shared_mutex> wr(ds->maps_mu);
-        auto it = ds->scratch.find(st);
-        if (it == ds->scratch.end()) {
-            BKD_HIP(hipStreamSynchronize(st));
+        std::unique_lock<std::shared_mutex> wr(call.ds->maps_mu);
+        auto it = call.ds->scratch.find(call.st);
+        if (it == call.ds->scratch.end()) {
+            BKD_HIP(hipStreamSynchronize(call.st));
             return BKD_OK;
         }
         sc = std::move(it->second);
-        ds->scratch.erase(it);
+        call.ds->scratch.erase(it);
     }
     int status = BKD_OK;
     {
         std::lock_guard<std::recursive_mutex> lk(sc->mu);
-        BKD_HIP(hipStreamSynchronize(st));  // the stream's kernels are done with the scratch
+        BKD_HIP(hipStreamSynchronize(call.st));  // the stream's kernels are done with the scratch
         if (sc->err) {
             BKD_HIP(hipMemcpy(sc->h_err, sc->err, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (*sc->h_err) status = fail(BKD_ERR_BOUNDS, "an indexed entry exceeded its base buffer (entries skipped, out = 0)");
+            if (*sc->h_err) status = fail(BKD_ERR_BOUNDS, kBoundsMsg);
         }
-        BKD_HIP(hipStreamSynchronize(st));  // the stream's own work is done with them
+        BKD_HIP(hipStreamSynchronize(call.st));  // the stream's own work is done with them
         for (int k = 0; k < 3; ++k)
             if (sc->buf[k]) BKD_HIP(hipFree(sc->buf[k]));
         for (uint32_t* w : {sc->err, sc->run, sc->uni, sc->vflag})
@@ -1470,21 +1415,16 @@ int bkd_crc_batch_host(int algo, const void* h_base, uint64_t base_size, const u
         bkd::host::crc_indexed(algo, (const uint8_t*)h_base, h_offsets, h_lengths, n, h_seeds, seed_all, h_out);
         return BKD_OK;
     }
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(nullptr, scope, &ds);
-    if (rc) return rc;
-    StageLease lease((int)(ds - g_dev));
-    HostStage& hs = *lease;
-    rc = hs.init();
-    if (rc) return rc;
-    if (!sorted) return host_batch_oneshot(*ds, hs, algo, (const uint8_t*)h_base, base_size, h_offsets, h_lengths, n,
+    StagedCall call;
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    if (!sorted) return host_batch_oneshot(*call.ds, hs, algo, (const uint8_t*)h_base, base_size, h_offsets, h_lengths, n,
                                            h_seeds, seed_all, h_out);
     uint64_t pieces = 0;
     for (uint64_t i = 0; i < n; ++i)
         if (h_lengths[i] > HostStage::kSeg) pieces += (h_lengths[i] + HostStage::kSeg - 1) / HostStage::kSeg - 1;
     if (pieces == 0)
-        return host_batch_pipelined(*ds, hs, algo, (const uint8_t*)h_base, h_offsets, h_lengths, n, h_seeds, seed_all,
+        return host_batch_pipelined(*call.ds, hs, algo, (const uint8_t*)h_base, h_offsets, h_lengths, n, h_seeds, seed_all,
                                     h_out);
     // Entries longer than a staging segment go through the pipeline as segment-sized pieces (the
     // first with the entry's seed, the others with seed ~0, i.e. their zero-initialised registers)
@@ -1510,10 +1450,10 @@ int bkd_crc_batch_host(int algo, const void* h_base, uint64_t base_size, const u
     // batch takes the one-copy route instead
     for (uint64_t j = 1; j < m; ++j)
         if (off2[j] < off2[j - 1])
-            return host_batch_oneshot(*ds, hs, algo, (const uint8_t*)h_base, base_size, h_offsets, h_lengths, n,
+            return host_batch_oneshot(*call.ds, hs, algo, (const uint8_t*)h_base, base_size, h_offsets, h_lengths, n,
                                       h_seeds, seed_all, h_out);
-    rc = host_batch_pipelined(*ds, hs, algo, (const uint8_t*)h_base, off2.data(), len2.data(), m, seed2.data(), 0,
-                              out2.data());
+    const int rc = host_batch_pipelined(*call.ds, hs, algo, (const uint8_t*)h_base, off2.data(), len2.data(), m, seed2.data(),
+                                        0, out2.data());
     if (rc) return rc;
     const uint32_t xseg = bkd::gf2::xpow(algo, 8ull * HostStage::kSeg);
     for (uint64_t i = 0, j = 0; i < n; ++i) {
@@ -1592,7 +1532,8 @@ int bkd_resume(int algo, uint32_t current, const void* ptr, uint64_t len, uint32
     // a device buffer runs on the null stream, which orders the call after the work queued on
     // the blocking streams (PyTorch's default stream among them) that may still be writing it
     int pdev = -1;
-    if (visible_devices() > 0 && is_device_pointer(ptr, &pdev)) {
+    const hipMemoryType where = visible_devices() > 0 ? pointer_type(ptr, &pdev) : hipMemoryTypeUnregistered;
+    if (where == hipMemoryTypeDevice || where == hipMemoryTypeManaged) {
         // on the null stream of the device that holds the buffer (not whichever is current)
         int cur = 0;
         BKD_HIP(hipGetDevice(&cur));
@@ -1683,17 +1624,14 @@ int bkd_digest_package_batch(int algo, int64_t ledger_id, const int64_t* d_entry
                              const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, void* d_frames,
                              uint64_t frame_stride, uint32_t* d_digests, void* stream) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_frames || !d_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    return package_framed(*ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return package_framed(*call.ds, call.st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
                           d_offsets, d_lengths, n, d_frames, frame_stride, d_digests);
 }
 
@@ -1705,12 +1643,9 @@ int bkd_digest_verify_batch(int algo, int64_t ledger_id, int64_t first_entry_id,
     if (!d_first_bad) return fail(BKD_ERR_INVALID_ARG, "null first_bad");
     if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    return verify_framed(*ds, st, algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0, d_framed, framed_size,
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return verify_framed(*call.ds, call.st, algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0, d_framed, framed_size,
                          d_offsets, d_lengths, n, d_status, d_first_bad);
 }
 
@@ -1724,30 +1659,24 @@ int bkd_digest_verify_batch_host(int algo, int64_t ledger_id, int64_t first_entr
     if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     for (uint64_t i = 0; i < n; ++i)
         if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
-    const int route = host_route(any_longer(h_lengths, n, HostStage::kSeg));
+    const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
         *h_first_bad = bkd::host::verify_frames(algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0,
                                                 (const uint8_t* const*)h_frames, h_lengths, n, h_status);
         return BKD_OK;
     }
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(nullptr, scope, &ds);
-    if (rc) return rc;
-    StageLease lease((int)(ds - g_dev));
-    HostStage& hs = *lease;
-    if ((rc = hs.init()) || (rc = hs.init_verify())) return rc;
+    StagedCall call(&HostStage::init_verify);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
     const int id_checks = skip_entry_check ? 1 : 0;
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        gather_entries(h_frames + i0, h_lengths + i0, cnt, hs.h_pin[s], hs.h_off[s]);
         const hipStream_t st = hs.st[s];
-        BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_len[s], h_lengths + i0, cnt * 4, hipMemcpyHostToDevice, st));
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
+        if (r) return r;
         uint64_t* d_fb = hs.d_fb[s];
-        int r = verify_framed(*ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s], bytes,
-                              hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
+        r = verify_framed(*call.ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s], bytes,
+                          hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
         if (r) return r;
         BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
         BKD_HIP(hipMemcpyAsync(hs.h_fb[s], d_fb, 8, hipMemcpyDeviceToHost, st));
@@ -1755,8 +1684,7 @@ int bkd_digest_verify_batch_host(int algo, int64_t ledger_id, int64_t first_entr
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
         memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        const uint64_t fb = *hs.h_fb[s];
-        if (fb < cnt && i0 + fb < *h_first_bad) *h_first_bad = i0 + fb;
+        merge_first_bad(hs, s, i0, cnt, h_first_bad);
         return BKD_OK;
     };
     return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
@@ -1767,7 +1695,7 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   const uint32_t* h_lengths, uint64_t n, void* h_frames, uint64_t frame_stride,
                                   uint32_t* h_digests) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_frames || !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
@@ -1775,7 +1703,7 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
         return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
     for (uint64_t i = 0; i < n; ++i)
         if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
-    const int route = host_route(any_longer(h_lengths, n, HostStage::kSeg));
+    const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
         bkd::host::package_frames(algo, ledger_id, h_entry_ids, h_lacs, h_length_fields,
@@ -1783,28 +1711,22 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   h_digests);
         return BKD_OK;
     }
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(nullptr, scope, &ds);
-    if (rc) return rc;
-    StageLease lease((int)(ds - g_dev));
-    HostStage& hs = *lease;
-    if ((rc = hs.init()) || (rc = hs.init_package())) return rc;
+    StagedCall call(&HostStage::init_package);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
     const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / frame_stride);
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        gather_entries(h_payloads + i0, h_lengths + i0, cnt, hs.h_pin[s], hs.h_off[s]);
+        const hipStream_t st = hs.st[s];
+        int r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        if (r) return r;
         int64_t* aux = reinterpret_cast<int64_t*>(hs.h_aux[s]);
         memcpy(aux, h_entry_ids + i0, cnt * 8);
         memcpy(aux + cnt, h_lacs + i0, cnt * 8);
         memcpy(aux + 2 * cnt, h_length_fields + i0, cnt * 8);
-        const hipStream_t st = hs.st[s];
-        BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_len[s], h_lengths + i0, cnt * 4, hipMemcpyHostToDevice, st));
         BKD_HIP(hipMemcpyAsync(hs.d_aux[s], aux, cnt * 24, hipMemcpyHostToDevice, st));
         const int64_t* d_aux = reinterpret_cast<const int64_t*>(hs.d_aux[s]);
-        int r = package_framed(*ds, st, algo, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
-                               hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], frame_stride, hs.d_res[s]);
+        r = package_framed(*call.ds, st, algo, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
+                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], frame_stride, hs.d_res[s]);
         if (r) return r;
         BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * frame_stride, hipMemcpyDeviceToHost, st));
         BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
@@ -1829,19 +1751,16 @@ int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id
     if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
     if (n && !d_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
-    const uint32_t mac = algo == BKD_CRC32C ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     if (n && d_out_frames) {
         if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
         const uint64_t fr0 = (uint64_t)(uintptr_t)d_out_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
         const uint64_t in0 = (uint64_t)(uintptr_t)d_framed, in1 = in0 + framed_size;
         if (fr0 < in1 && in0 < fr1) return fail(BKD_ERR_INVALID_ARG, "out_frames overlaps the framed buffer");
     }
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    return reframe_framed(*ds, st, algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0,
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return reframe_framed(*call.ds, call.st, algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0,
                           (flags & BKD_REFRAME_TRUSTED) != 0, d_framed, framed_size, d_offsets, d_lengths, n, d_new_lacs,
                           d_out_frames, frame_stride, d_digests, d_status, d_first_bad);
 }
@@ -1861,7 +1780,7 @@ int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_ent
         if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
     const bool trusted = (flags & BKD_REFRAME_TRUSTED) != 0;
     const int id_checks = skip_entry_check ? 1 : 0;
-    const int route = host_route(any_longer(h_lengths, n, HostStage::kSeg));
+    const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
         *h_first_bad = bkd::host::reframe_frames(algo, ledger_id, first_entry_id, id_checks, trusted,
@@ -1869,27 +1788,21 @@ int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_ent
                                                  h_status);
         return BKD_OK;
     }
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(nullptr, scope, &ds);
-    if (rc) return rc;
-    StageLease lease((int)(ds - g_dev));
-    HostStage& hs = *lease;
-    if ((rc = hs.init()) || (rc = hs.init_verify()) || (rc = hs.init_reframe())) return rc;
+    StagedCall call(&HostStage::init_verify, &HostStage::init_reframe);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
     // staged as verify; the device reframes its copy in place and only status and digests come back
     // (d_seed / h_seed carry the digests), then the host threads write each OK frame's 12 bytes
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        gather_entries(h_frames + i0, h_lengths + i0, cnt, hs.h_pin[s], hs.h_off[s]);
-        memcpy(hs.h_lac[s], h_new_lacs + i0, cnt * 8);
         const hipStream_t st = hs.st[s];
-        BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_len[s], h_lengths + i0, cnt * 4, hipMemcpyHostToDevice, st));
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        memcpy(hs.h_lac[s], h_new_lacs + i0, cnt * 8);
         BKD_HIP(hipMemcpyAsync(hs.d_lac[s], hs.h_lac[s], cnt * 8, hipMemcpyHostToDevice, st));
         uint64_t* d_fb = hs.d_fb[s];
-        int r = reframe_framed(*ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, trusted, hs.d_buf[s],
-                               bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_lac[s], nullptr, 0, hs.d_seed[s],
-                               reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
+        r = reframe_framed(*call.ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, trusted, hs.d_buf[s],
+                           bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_lac[s], nullptr, 0, hs.d_seed[s],
+                           reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
         if (r) return r;
         BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
         BKD_HIP(hipMemcpyAsync(hs.h_seed[s], hs.d_seed[s], cnt * 4, hipMemcpyDeviceToHost, st));
@@ -1901,8 +1814,7 @@ int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_ent
         if (h_digests) memcpy(h_digests + i0, hs.h_seed[s], cnt * 4);
         bkd::host::apply_reframe(algo, (uint8_t* const*)h_frames + i0, cnt, h_new_lacs + i0,
                                  reinterpret_cast<const int32_t*>(hs.h_res[s]), hs.h_seed[s]);
-        const uint64_t fb = *hs.h_fb[s];
-        if (fb < cnt && i0 + fb < *h_first_bad) *h_first_bad = i0 + fb;
+        merge_first_bad(hs, s, i0, cnt, h_first_bad);
         return BKD_OK;
     };
     return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
@@ -1915,12 +1827,9 @@ int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const ui
     if (!d_first_bad) return fail(BKD_ERR_INVALID_ARG, "null first_bad");
     if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (n && !d_log) return fail(BKD_ERR_INVALID_ARG, "null log buffer");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    return verify_framed(*ds, st, algo, 0, 0, 2, d_log, log_size, d_offsets, d_lengths, n, d_status, d_first_bad);
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return verify_framed(*call.ds, call.st, algo, 0, 0, 2, d_log, log_size, d_offsets, d_lengths, n, d_status, d_first_bad);
 }
 
 int bkd_crc_batch_segments(int algo, const void* d_base, uint64_t base_size, const uint64_t* d_seg_offsets,
@@ -1931,27 +1840,24 @@ int bkd_crc_batch_segments(int algo, const void* d_base, uint64_t base_size, con
     if (!d_seg_first || !d_out || (nseg && (!d_seg_offsets || !d_seg_lengths)))
         return fail(BKD_ERR_INVALID_ARG, "null index/out");
     if (nseg && !d_base && base_size) return fail(BKD_ERR_INVALID_ARG, "null base");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
-    StreamScratch& sc = scratch_for(*ds, st);
+    Call call(stream);
+    if (call.rc) return call.rc;
+    StreamScratch& sc = scratch_for(*call.ds, call.st);
     std::lock_guard<std::recursive_mutex> lk(sc.mu);  // held across the nested plan (slot 0)
     uint8_t* seg = nullptr;
-    hipError_t e = sc.get(2, (size_t)std::max<uint64_t>(nseg, 1) * 4, st, &seg);
+    hipError_t e = sc.get(2, (size_t)std::max<uint64_t>(nseg, 1) * 4, call.st, &seg);
     if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("segment scratch: ") + hipGetErrorString(e));
     uint32_t* segcrc = reinterpret_cast<uint32_t*>(seg);
     // every segment's raw register reg(0, segment), as ~resume(~0, segment)
     if (nseg) {
-        rc = indexed_batch(*ds, algo, (const uint8_t*)d_base, base_size, d_seg_offsets, d_seg_lengths, nseg, nullptr,
-                           0xFFFFFFFFu, segcrc, st);
+        const int rc = indexed_batch(*call.ds, algo, (const uint8_t*)d_base, base_size, d_seg_offsets, d_seg_lengths,
+                                     nseg, nullptr, 0xFFFFFFFFu, segcrc, call.st);
         if (rc) return rc;
     }
     bkd::XPow8 pw;
     for (int b = 0; b < 32; ++b) pw.p[b] = bkd::gf2::xpow(algo, 8ull << b);
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(bkd::segments_combine_kernel, dim3(blocks), dim3(256), 0, st, d_seg_lengths, segcrc,
+    hipLaunchKernelGGL(bkd::segments_combine_kernel, dim3(blocks), dim3(256), 0, call.st, d_seg_lengths, segcrc,
                        d_seg_first, n, nseg, d_seeds, seed_all, pw, bkd::gf2::poly(algo), d_out);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
@@ -2007,14 +1913,11 @@ int bkd_entrylog_index(const void* h_log, uint64_t log_size, uint64_t start, uin
 int bkd_fill_splitmix64(void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t first_word, void* stream) {
     if (nbytes == 0) return BKD_OK;
     if (!d_dst) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    const hipStream_t st = (hipStream_t)stream;
-    DeviceScope scope;
-    DeviceState* ds = nullptr;
-    int rc = enter(st, scope, &ds);
-    if (rc) return rc;
+    Call call(stream);
+    if (call.rc) return call.rc;
     const uint64_t nw = std::max<uint64_t>(1, nbytes / 8);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((nw + 255) / 256, (uint64_t)ds->cus * 16);
-    hipLaunchKernelGGL(bkd::fill_splitmix64_kernel, dim3(blocks), dim3(256), 0, st,
+    const unsigned blocks = (unsigned)std::min<uint64_t>((nw + 255) / 256, (uint64_t)call.ds->cus * 16);
+    hipLaunchKernelGGL(bkd::fill_splitmix64_kernel, dim3(blocks), dim3(256), 0, call.st,
                        (uint8_t*)d_dst, nbytes, seed, first_word);
     BKD_HIP(hipGetLastError());
     return BKD_OK;

@@ -141,9 +141,52 @@ void for_chunks(uint64_t n, const uint32_t* lens, Body&& body) {
 constexpr uint64_t kPieceBytes = 1u << 20;
 constexpr uint64_t kSplitBytes = 4u << 20;
 
-inline bool split_on() { return Pool::get().active() > 1; }
-
 inline bool is_big(uint64_t len) { return len >= kSplitBytes; }
+
+// The walk of every batch: one(i, whole_pool, ctx) for the entries below kSplitBytes in chunks over
+// the pool (whole_pool = false; a fresh Ctx per chunk), then for the others one after another, each
+// folded on the whole pool (split = false: all in the chunks, as with one thread). Returns the
+// smallest i whose one() returned non-zero, n when none did.
+template <class Ctx = char, class One>
+uint64_t walk(uint64_t n, const uint32_t* lens, bool split, One&& one) {
+    split = split && Pool::get().active() > 1;
+    std::atomic<bool> big{false};
+    std::atomic<uint64_t> first_bad{n};
+    auto note_bad = [&](uint64_t bad) {
+        uint64_t cur = first_bad.load(std::memory_order_relaxed);
+        while (bad < cur && !first_bad.compare_exchange_weak(cur, bad, std::memory_order_relaxed)) {
+        }
+    };
+    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
+        uint64_t bad = n;
+        Ctx ctx{};
+        for (uint64_t i = i0; i < i1; ++i) {
+            if (split && is_big(lens[i])) {
+                big.store(true, std::memory_order_relaxed);
+                continue;
+            }
+            if (one(i, false, ctx) != 0 && i < bad) bad = i;
+        }
+        note_bad(bad);
+    });
+    if (big.load()) {
+        Ctx ctx{};
+        for (uint64_t i = 0; i < n; ++i)
+            if (is_big(lens[i]) && one(i, true, ctx) != 0) note_bad(i);
+    }
+    return first_bad.load();
+}
+
+// out[i] = resume(seed_i, the lens[i] bytes at at(i))
+template <class At>
+void crc_entries(int algo, At&& at, const uint32_t* lens, uint64_t n, const uint32_t* seeds, uint32_t seed_all,
+                 uint32_t* out) {
+    walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
+        const uint32_t seed = seeds ? seeds[i] : seed_all;
+        out[i] = !lens[i] ? seed : whole_pool ? ~fold(algo, ~seed, at(i), lens[i]) : ~crc_raw(algo, ~seed, at(i), lens[i]);
+        return 0;
+    });
+}
 
 inline uint32_t be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
@@ -236,78 +279,22 @@ uint32_t fold(int algo, uint32_t reg, const uint8_t* p, uint64_t len) {
 
 void crc_list(int algo, const uint8_t* const* ptrs, const uint32_t* lens, uint64_t n, const uint32_t* seeds,
               uint32_t seed_all, uint32_t* out) {
-    const bool split = split_on();
-    std::atomic<bool> big{false};
-    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
-        for (uint64_t i = i0; i < i1; ++i) {
-            if (split && is_big(lens[i])) {
-                big.store(true, std::memory_order_relaxed);
-                continue;
-            }
-            const uint32_t seed = seeds ? seeds[i] : seed_all;
-            out[i] = lens[i] ? ~crc_raw(algo, ~seed, ptrs[i], lens[i]) : seed;
-        }
-    });
-    if (big.load())
-        for (uint64_t i = 0; i < n; ++i)
-            if (is_big(lens[i])) out[i] = ~fold(algo, ~(seeds ? seeds[i] : seed_all), ptrs[i], lens[i]);
+    crc_entries(algo, [&](uint64_t i) { return ptrs[i]; }, lens, n, seeds, seed_all, out);
 }
 
 void crc_indexed(int algo, const uint8_t* base, const uint64_t* offsets, const uint32_t* lens, uint64_t n,
                  const uint32_t* seeds, uint32_t seed_all, uint32_t* out) {
-    const bool split = split_on();
-    std::atomic<bool> big{false};
-    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
-        for (uint64_t i = i0; i < i1; ++i) {
-            if (split && is_big(lens[i])) {
-                big.store(true, std::memory_order_relaxed);
-                continue;
-            }
-            const uint32_t seed = seeds ? seeds[i] : seed_all;
-            out[i] = lens[i] ? ~crc_raw(algo, ~seed, base + offsets[i], lens[i]) : seed;
-        }
-    });
-    if (big.load())
-        for (uint64_t i = 0; i < n; ++i)
-            if (is_big(lens[i])) out[i] = ~fold(algo, ~(seeds ? seeds[i] : seed_all), base + offsets[i], lens[i]);
+    crc_entries(algo, [&](uint64_t i) { return base + offsets[i]; }, lens, n, seeds, seed_all, out);
 }
 
 // DigestManager.verifyDigest per frame (frame_status).
 uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks,
                        const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
-    const uint32_t mac = algo == 0 ? 4u : 8u;
-    const bool split = split_on();
-    std::atomic<bool> big{false};
-    auto one = [&](uint64_t i, bool whole_pool) -> int32_t {
-        return frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, frames[i], lens[i],
-                            whole_pool, true);
-    };
-    std::atomic<uint64_t> first_bad{n};
-    auto note_bad = [&](uint64_t bad) {
-        uint64_t cur = first_bad.load(std::memory_order_relaxed);
-        while (bad < cur && !first_bad.compare_exchange_weak(cur, bad, std::memory_order_relaxed)) {
-        }
-    };
-    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
-        uint64_t bad = n;
-        for (uint64_t i = i0; i < i1; ++i) {
-            if (split && is_big(lens[i])) {
-                big.store(true, std::memory_order_relaxed);
-                continue;
-            }
-            const int32_t st = one(i, false);
-            status[i] = st;
-            if (st != 0 && i < bad) bad = i;
-        }
-        note_bad(bad);
+    const uint32_t mac = mac_len(algo);
+    return walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
+        return status[i] = frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, frames[i], lens[i],
+                                        whole_pool, true);
     });
-    if (big.load())
-        for (uint64_t i = 0; i < n; ++i)
-            if (is_big(lens[i])) {
-                status[i] = one(i, true);
-                if (status[i] != 0) note_bad(i);
-            }
-    return first_bad.load();
 }
 
 // DigestManager.computeDigestAndPackageForSending (:117-181): header [ledgerId, entryId, LAC, length]
@@ -316,10 +303,8 @@ uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int 
 void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                     const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
                     uint8_t* frames, uint64_t stride, uint32_t* digests) {
-    const uint32_t mac = algo == 0 ? 4u : 8u;
-    const bool split = split_on();
-    std::atomic<bool> big{false};
-    auto one = [&](uint64_t i, bool whole_pool) {
+    const uint32_t mac = mac_len(algo);
+    walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
         uint8_t* f = frames + i * stride;
         put_be64(f, (uint64_t)ledger_id);
         put_be64(f + 8, (uint64_t)entry_ids[i]);
@@ -331,19 +316,8 @@ void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const
         if (mac == 8u) put_be32(f + 32, 0u);
         put_be32(f + 32 + (mac - 4u), d);
         digests[i] = d;
-    };
-    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
-        for (uint64_t i = i0; i < i1; ++i) {
-            if (split && is_big(lens[i])) {
-                big.store(true, std::memory_order_relaxed);
-                continue;
-            }
-            one(i, false);
-        }
+        return 0;
     });
-    if (big.load())
-        for (uint64_t i = 0; i < n; ++i)
-            if (is_big(lens[i])) one(i, true);
 }
 
 // LedgerFragmentReplicator's second framing of an entry it has read and verified
@@ -353,10 +327,9 @@ void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const
 uint64_t reframe_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks, bool trusted,
                         uint8_t* const* frames, const uint32_t* lens, uint64_t n, const int64_t* new_lacs,
                         uint32_t* digests, int32_t* status) {
-    const uint32_t mac = algo == 0 ? 4u : 8u;
-    const bool split = split_on() && !trusted;  // a trusted frame's payload is not read: nothing to split
-    std::atomic<bool> big{false};
-    auto one = [&](uint64_t i, bool whole_pool, PowCache& pw) -> int32_t {
+    const uint32_t mac = mac_len(algo);
+    // (a trusted frame's payload is not read: nothing to split)
+    return walk<PowCache>(n, lens, !trusted, [&](uint64_t i, bool whole_pool, PowCache& pw) {
         uint8_t* f = frames[i];
         const int32_t st = frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, f, lens[i],
                                         whole_pool, !trusted);
@@ -369,42 +342,13 @@ uint64_t reframe_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int
             put_be32(f + 32 + (mac - 4u), d);  // (CRC32's high word is zero in a frame that is OK)
         }
         if (digests) digests[i] = d;
-        return st;
-    };
-    std::atomic<uint64_t> first_bad{n};
-    auto note_bad = [&](uint64_t bad) {
-        uint64_t cur = first_bad.load(std::memory_order_relaxed);
-        while (bad < cur && !first_bad.compare_exchange_weak(cur, bad, std::memory_order_relaxed)) {
-        }
-    };
-    for_chunks(n, lens, [&](uint64_t i0, uint64_t i1) {
-        uint64_t bad = n;
-        PowCache pw;
-        for (uint64_t i = i0; i < i1; ++i) {
-            if (split && is_big(lens[i])) {
-                big.store(true, std::memory_order_relaxed);
-                continue;
-            }
-            const int32_t st = one(i, false, pw);
-            status[i] = st;
-            if (st != 0 && i < bad) bad = i;
-        }
-        note_bad(bad);
+        return status[i] = st;
     });
-    if (big.load()) {
-        PowCache pw;
-        for (uint64_t i = 0; i < n; ++i)
-            if (is_big(lens[i])) {
-                status[i] = one(i, true, pw);
-                if (status[i] != 0) note_bad(i);
-            }
-    }
-    return first_bad.load();
 }
 
 void apply_reframe(int algo, uint8_t* const* frames, uint64_t n, const int64_t* new_lacs, const int32_t* status,
                    const uint32_t* digests) {
-    const uint32_t mac = algo == 0 ? 4u : 8u;
+    const uint32_t mac = mac_len(algo);
     for_chunks(n, nullptr, [&](uint64_t i0, uint64_t i1) {
         for (uint64_t i = i0; i < i1; ++i) {
             if (status[i] != 0) continue;

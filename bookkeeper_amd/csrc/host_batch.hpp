@@ -49,6 +49,10 @@ class Pool {
     bool stop_ = false;
 };
 
+// Bytes of the digest after a frame's 32-byte header: CRC32C writes an int, CRC32 a long
+// (CRC32CDigestManager.java:44-46, CRC32DigestManager.java:60-63).
+inline uint32_t mac_len(int algo) { return algo == 0 ? 4u : 8u; }
+
 // ---- the CPU route of host-resident batches (semantics of include/bkdigest.h) ----
 // The register after folding p[0, len) onto reg; from 4 MiB on in 1 MiB pieces over the pool,
 // joined with x^(8 * piece) (one long buffer uses every core, not one).

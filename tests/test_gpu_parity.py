@@ -471,6 +471,32 @@ def test_package_batch_frame_strides(gpu, dtype, algo, stride):
         assert frames[i, :hl].tobytes() == hdr + oracle.digest_bytes(algo, d), i
 
 
+@pytest.mark.parametrize("lanes", [4, 16, 32])
+def test_package_fused_forced_lane_widths(gpu, lanes):
+    """crc_package_fused_kernel at the lane counts that no automatic choice of the tests above reaches
+    (they take 8 or 64): 64 entries x 1 KiB with the group width forced, frames in a buffer of their own."""
+    import torch
+    n, L = 64, 1024
+    payload = oracle.fill_splitmix64(n * L, 31 + lanes)
+    ids = np.arange(n, dtype=np.int64) + 7
+    dm = dg.DigestManager.instantiate(9, b"", dg.DigestType.CRC32C, False)
+    ck.set_group_lanes(lanes)
+    try:
+        frames, digests = dm.package_batch(torch.from_numpy(ids).to(gpu), torch.from_numpy(ids - 1).to(gpu),
+                                           torch.full((n,), L, dtype=torch.int64, device=gpu),
+                                           _dev_bytes(torch, payload, gpu),
+                                           torch.arange(n, dtype=torch.int64, device=gpu) * L,
+                                           torch.full((n,), L, dtype=torch.int32, device=gpu), sync_check=True)
+    finally:
+        ck.set_group_lanes(0)
+    frames = frames.cpu().numpy()
+    digests = digests.cpu().numpy().view(np.uint32)
+    for i in range(n):
+        d, hdr = oracle.digest_entry(ck.CRC32C, 9, int(ids[i]), int(ids[i]) - 1, L, payload[i * L:(i + 1) * L])
+        assert digests[i] == d, i
+        assert frames[i, :36].tobytes() == hdr + oracle.digest_bytes(ck.CRC32C, d), i
+
+
 @pytest.mark.parametrize("dtype,algo", [(dg.DigestType.CRC32C, ck.CRC32C), (dg.DigestType.CRC32, ck.CRC32)])
 def test_package_in_place_and_apart_routes_agree(gpu, dtype, algo):
     """bkd_digest_package_batch with the frames written in front of their own payloads (one buffer:
@@ -1153,3 +1179,50 @@ def test_plan_held_partials_past_one_flush(gpu, algo):
         data = base[o_np[i]:o_np[i] + l_np[i]].cpu().numpy()
         assert planned[i] == oracle.resume(algo, 0, data), i
     del base
+
+
+_PREFETCH_BATCH = {}
+
+
+def _prefetch_batch():
+    """The batch of test_plan_prefetch_depths and its oracle digests, computed once for all cases."""
+    if not _PREFETCH_BATCH:
+        rng = np.random.default_rng(2024)
+        n = 512
+        fixed = [0, 1, 15, 16, 17, 127, 128, 129, 4095, 4096, 4097, 70_000]
+        lens = np.concatenate([fixed, rng.integers(0, 70_001, n - len(fixed))]).astype(np.int64)
+        gaps = 1 + 2 * rng.integers(0, 40, n)  # odd gaps: the offsets take every alignment
+        offs = (np.concatenate([[0], np.cumsum(lens + gaps)[:-1]]) + 3).astype(np.int64)
+        data = oracle.fill_splitmix64(int(offs[-1] + lens[-1]) + 64, 77)
+        seeds = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
+        want = {(algo, per_entry): oracle.batch(algo, data, offs, lens, seeds=seeds if per_entry else None,
+                                                seed_all=0x1234ABCD)
+                for algo in (ck.CRC32C, ck.CRC32) for per_entry in (False, True)}
+        _PREFETCH_BATCH.update(data=data, offs=offs, lens=lens, seeds=seeds, want=want)
+    return _PREFETCH_BATCH
+
+
+@pytest.mark.parametrize("algo", [ck.CRC32C, ck.CRC32])
+@pytest.mark.parametrize("pf", [2, 4, 8])
+def test_plan_prefetch_depths(gpu, algo, pf):
+    """bkd_set_plan_prefetch: the chunk kernel with 2, 4 and 8 loads in flight per lane, in plan mode 2.
+    512 entries at unaligned offsets, the lengths around every step, line and chunk boundary plus random
+    ones up to 70 000; one seed for all entries (depth 2 then takes the 8-byte descriptors) and per-entry
+    seeds. Every digest equals the oracle's."""
+    import torch
+    b = _prefetch_batch()
+    base = _dev_bytes(torch, b["data"], gpu)
+    d_off = torch.from_numpy(b["offs"]).to(gpu)
+    d_len = torch.from_numpy(b["lens"].astype(np.int32)).to(gpu)
+    d_seeds = torch.from_numpy(b["seeds"].view(np.int32)).to(gpu)
+    ck.set_plan_mode(2)
+    ck.set_plan_prefetch(pf)
+    try:
+        for per_entry in (False, True):
+            got = ck.crc_batch(algo, base, d_off, d_len, seeds=d_seeds if per_entry else None, seed_all=0x1234ABCD,
+                               sync_check=True).cpu().numpy().view(np.uint32)
+            bad = np.nonzero(got != b["want"][(algo, per_entry)])[0]
+            assert bad.size == 0, (per_entry, bad[:5].tolist(), b["lens"][bad[:5]].tolist())
+    finally:
+        ck.set_plan_prefetch(2)
+        ck.set_plan_mode(0)
