@@ -28,6 +28,7 @@ VERIFY_LEDGER_MISMATCH = 3
 VERIFY_ENTRY_MISMATCH = 4
 
 REFRAME_TRUSTED = 1  # BKD_REFRAME_TRUSTED
+REQUEST_SKIP_ENTRY_ID = 1  # BKD_REQUEST_SKIP_ENTRY_ID
 
 HEADER_PATH = os.path.join(ROOT, "include", "bkdigest.h")
 
@@ -75,6 +76,11 @@ PROTOTYPES = {
     "bkd_digest_package_batch_host": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "bkd_digest_package_batch": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
     "bkd_digest_verify_batch": (_int, [_int, _i64, _i64, _int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_digest_verify_requests": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bkd_digest_package_batch_ledgers": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp,
+                                                _vp]),
+    "bkd_digest_verify_requests_host": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "bkd_digest_package_batch_ledgers_host": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "bkd_digest_reframe_batch": (_int, [_int, _i64, _i64, _int, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
                                         _vp, _vp, _vp]),
     "bkd_digest_reframe_batch_host": (_int, [_int, _i64, _i64, _int, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),

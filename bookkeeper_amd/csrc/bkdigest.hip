@@ -580,6 +580,11 @@ struct HostStage {
     // reframe: the new LACs in (8 B per entry); its digests come back through d_seed / h_seed
     bool lac_ready = false;
     int64_t *h_lac[2] = {}, *d_lac[2] = {};
+    // verify requests: per-entry expectations in (8 + 8 + 4 B per entry), then one zero u64 (the
+    // segment's request 0 starts at its entry 0)
+    static constexpr size_t kRqBytes = kSegEntries * 20 + 8;
+    bool rq_ready = false;
+    uint8_t *h_rq[2] = {}, *d_rq[2] = {};
     // Every buffer is made by pin() (pinned host) or dev() (device), which record it for the
     // destructor. Each allocation is made once: a call after a failed init*() completes the set,
     // nothing leaks.
@@ -627,6 +632,13 @@ struct HostStage {
         for (int s = 0, rc; s < 2; ++s)
             if ((rc = pin(h_fb[s], sizeof(uint64_t))) || (rc = dev(d_fb[s], sizeof(uint64_t)))) return rc;
         fb_ready = true;
+        return BKD_OK;
+    }
+    int init_requests() {
+        if (rq_ready) return BKD_OK;
+        for (int s = 0, rc; s < 2; ++s)
+            if ((rc = pin(h_rq[s], kRqBytes)) || (rc = dev(d_rq[s], kRqBytes))) return rc;
+        rq_ready = true;
         return BKD_OK;
     }
     int init_reframe() {
@@ -902,10 +914,13 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
 // Fused route (4..64-lane groups, frames apart from the payload): each lane group builds its
 // entry's header from the index arrays and folds header + payload in one pass, storing the digest
 // (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
+// d_ledger_ids (bkd_digest_package_batch_ledgers): one ledger id per entry instead of ledger_id; the
+// same routes through the *_ledgers_kernel forms, which read ledger_ids[i] beside entry_ids[i].
 int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_entry_ids,
                    const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
                    uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
-                   void* d_frames, uint64_t frame_stride, uint32_t* d_digests) {
+                   void* d_frames, uint64_t frame_stride, uint32_t* d_digests,
+                   const int64_t* d_ledger_ids = nullptr) {
     const uint32_t mac = mac_len(algo);
     const int lanes = auto_lanes(payload_size / n, n, ds.cus);
     const uint32_t* tab = ds.tables[algo][lane_index(lanes)];
@@ -922,22 +937,36 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     if (lanes >= 4 && frames_apart) {
         rc = with_lanes<4>(lanes, [&](auto g) -> int {
             constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
-                               dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths, n,
-                               ledger_id, d_entry_ids, d_lacs, d_length_fields, ds.tables[algo][lane_index(G)],
-                               d_digests, err, g_fold_sched.load());
+            if (d_ledger_ids)
+                hipLaunchKernelGGL((bkd::crc_package_fused_ledgers_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths,
+                                   n, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields,
+                                   ds.tables[algo][lane_index(G)], d_digests, err, g_fold_sched.load());
+            else
+                hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths,
+                                   n, ledger_id, d_entry_ids, d_lacs, d_length_fields, ds.tables[algo][lane_index(G)],
+                                   d_digests, err, g_fold_sched.load());
             BKD_HIP(hipGetLastError());
             return BKD_OK;
         });
         if (rc) return rc;
-        hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
-                           d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
+        if (d_ledger_ids)
+            hipLaunchKernelGGL(bkd::package_frame_ledgers_kernel, dim3(blocks), dim3(256), 0, st, d_ledger_ids,
+                               d_entry_ids, d_lacs, d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
+        else
+            hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
+                               d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
         BKD_HIP(hipGetLastError());
         return BKD_OK;
     }
     const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
-    hipLaunchKernelGGL(bkd::package_header_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, ledger_id, d_entry_ids,
-                       d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
+    if (d_ledger_ids)
+        hipLaunchKernelGGL(bkd::package_header_ledgers_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, d_ledger_ids,
+                           d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
+    else
+        hipLaunchKernelGGL(bkd::package_header_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, ledger_id,
+                           d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
     BKD_HIP(hipGetLastError());
     bkd::IndexedSrc src{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests};
     rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
@@ -954,12 +983,33 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
 // PlanRun::in_band of the first, the fused kernel verifies each frame whole (header, payload and
 // compare in one pass over it) and the header / plan / finish kernels return at once; otherwise
 // the fused kernel returns and they run. Both give the same statuses; the device decides, no sync.
+// The read requests of bkd_digest_verify_requests (device arrays; include/bkdigest.h).
+// expanded (the host-resident form's staged segments): exp_lid / exp_eid / req_of hold the per-entry
+// expectations already, no expansion runs, and `first` / `first_bad` are what req_of's request
+// indices refer to (one request 0 per segment: the host computes the prefixes from the statuses).
+struct Requests {
+    uint64_t nreq;
+    const uint64_t* first;
+    const int64_t *ledger_ids, *first_entry_ids;
+    const uint32_t* flags;
+    uint64_t* first_bad;
+    const int64_t *exp_lid = nullptr, *exp_eid = nullptr;
+    const uint32_t* req_of = nullptr;
+};
+
+// rq (bkd_digest_verify_requests): per-request ledger ids, first entry ids, skip flags and verified
+// prefixes instead of ledger_id / first_entry_id / id_checks / d_first_bad. One more launch at the
+// head (request_expand_kernel: the CSR into per-entry expectations in the stream's scratch, the CSR
+// checked, the prefixes initialised); then the same gate and the same two routes, through the
+// *_requests_kernel forms.
 int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, int64_t first_entry_id,
                   int id_checks, const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
-                  const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad) {
+                  const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad,
+                  const Requests* rq = nullptr) {
     const uint32_t mac = mac_len(algo);
     if (n == 0) {
-        BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
+        if (!rq) BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
+        else if (rq->nreq) BKD_HIP(hipMemsetAsync(rq->first_bad, 0, rq->nreq * sizeof(uint64_t), st));
         return BKD_OK;
     }
     const uint32_t* x32tab = ds.tables[algo][lane_index(4)] + 1024;  // x^32 operator, 4 x 256
@@ -967,6 +1017,11 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
     Carver cv;
     const size_t o_seeds = cv.take(n * 4), o_plen = cv.take(n * 4), o_poff = cv.take(n * 8), o_exp = cv.take(n * 4),
                  o_pre = cv.take(n * 4);
+    // requests: expected ledger and entry id and the request (bit 31: skip the entry-id check) per
+    // entry, and the word the gate stores n into in d_first_bad's place
+    const bool expand = rq && !rq->exp_lid;
+    const size_t o_xlid = cv.take(expand ? n * 8 : 0), o_xeid = cv.take(expand ? n * 8 : 0),
+                 o_req = cv.take(expand ? n * 4 : 0), o_fbw = cv.take(rq ? 8 : 0);
     StreamScratch& sc = scratch_for(ds, st);
     std::lock_guard<std::recursive_mutex> lk(sc.mu);  // held across the nested plan (slot 0)
     uint8_t* sb = nullptr;
@@ -977,6 +1032,24 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
     uint64_t* poff = Carver::at<uint64_t>(sb, o_poff);
     uint32_t* expect = Carver::at<uint32_t>(sb, o_exp);
     uint32_t* pre = Carver::at<uint32_t>(sb, o_pre);
+    bkd::RequestIds rids{};
+    if (rq) d_first_bad = Carver::at<uint64_t>(sb, o_fbw);
+    if (rq && !expand) rids = bkd::RequestIds{rq->exp_lid, rq->exp_eid, rq->req_of, rq->first, (unsigned long long*)rq->first_bad};
+    if (expand) {
+        uint32_t* err = nullptr;
+        const int rc = bounds_flag(ds, st, &err);
+        if (rc) return rc;
+        int64_t *xlid = Carver::at<int64_t>(sb, o_xlid), *xeid = Carver::at<int64_t>(sb, o_xeid);
+        uint32_t* req_of = Carver::at<uint32_t>(sb, o_req);
+        rids = bkd::RequestIds{xlid, xeid, req_of, rq->first, (unsigned long long*)rq->first_bad};
+        const unsigned xblocks =
+            (unsigned)std::min<uint64_t>((std::max(n, rq->nreq) + 255) / 256, 8u * (uint64_t)ds.cus);
+        hipLaunchKernelGGL(bkd::request_expand_kernel, dim3(xblocks), dim3(256), 0, st, rq->first, rq->nreq, n,
+                           rq->ledger_ids, rq->first_entry_ids, rq->flags, xlid, xeid, req_of,
+                           (unsigned long long*)rq->first_bad, err);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
+    }
     // the fused route where the payloads would take the plan (large batches; the direct kernel's small
     // ones keep the three-kernel sequence)
     // — and, as the plan's own near-uniform gate, only where one frame per group uses the plan's lane
@@ -1001,27 +1074,42 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
         // narrowest group, 4
         const int rc = with_lanes<4>(fused_lanes == 1 ? 4 : fused_lanes, [&](auto g) -> int {
             constexpr int G = decltype(g)::value;
-            hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
-                               dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n,
-                               mac, ledger_id, first_entry_id, id_checks, ds.tables[algo][lane_index(G)], d_status,
-                               (unsigned long long*)d_first_bad, vflag, vepoch, g_fold_sched.load());
+            if (rq)
+                hipLaunchKernelGGL((bkd::crc_verify_fused_requests_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths,
+                                   n, mac, rids, ds.tables[algo][lane_index(G)], d_status, vflag, vepoch,
+                                   g_fold_sched.load());
+            else
+                hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths,
+                                   n, mac, ledger_id, first_entry_id, id_checks, ds.tables[algo][lane_index(G)], d_status,
+                                   (unsigned long long*)d_first_bad, vflag, vepoch, g_fold_sched.load());
             const hipError_t le = hipGetLastError();
             return le == hipSuccess ? BKD_OK : fail(BKD_ERR_HIP, hipGetErrorString(le));
         });
         if (rc) return rc;
     }
     const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
-    hipLaunchKernelGGL(bkd::verify_header_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab, (const uint8_t*)d_framed,
-                       framed_size, d_offsets, d_lengths, n, mac, ledger_id, first_entry_id, id_checks, seeds, poff,
-                       plen, expect, pre, d_first_bad, vflag, vepoch);
+    if (rq)
+        hipLaunchKernelGGL(bkd::verify_header_requests_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab,
+                           (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n, mac, rids, seeds, poff, plen,
+                           expect, pre, vflag, vepoch);
+    else
+        hipLaunchKernelGGL(bkd::verify_header_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab, (const uint8_t*)d_framed,
+                           framed_size, d_offsets, d_lengths, n, mac, ledger_id, first_entry_id, id_checks, seeds, poff,
+                           plen, expect, pre, d_first_bad, vflag, vepoch);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
     // payload CRCs land in d_status, then verify_finish turns them into status codes
     int rc = indexed_batch(ds, algo, (const uint8_t*)d_framed, framed_size, poff, plen, n, seeds, 0,
                            reinterpret_cast<uint32_t*>(d_status), st, vflag, vepoch, route);
     if (rc) return rc;
-    hipLaunchKernelGGL(bkd::verify_finish_kernel, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status,
-                       (unsigned long long*)d_first_bad, vflag, vepoch);
+    if (rq)
+        hipLaunchKernelGGL(bkd::verify_finish_requests_kernel, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status,
+                           rids, vflag, vepoch);
+    else
+        hipLaunchKernelGGL(bkd::verify_finish_kernel, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status,
+                           (unsigned long long*)d_first_bad, vflag, vepoch);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
     return BKD_OK;
@@ -1225,6 +1313,44 @@ int resume_device(int algo, uint32_t current, const void* ptr, uint64_t len, hip
     }
     call_release(dev, c);
     return rc;
+}
+
+// The GPU route of bkd_digest_package_batch_host and bkd_digest_package_batch_ledgers_host
+// (h_ledger_ids: one ledger id per entry, staged as a fourth aux array; else ledger_id for all).
+int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                        const int64_t* h_lacs, const int64_t* h_length_fields, const void* const* h_payloads,
+                        const uint32_t* h_lengths, uint64_t n, void* h_frames, uint64_t frame_stride,
+                        uint32_t* h_digests) {
+    StagedCall call(&HostStage::init_package);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    const uint64_t fields = h_ledger_ids ? 4 : 3;
+    const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / frame_stride);
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        const hipStream_t st = hs.st[s];
+        int r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        int64_t* aux = reinterpret_cast<int64_t*>(hs.h_aux[s]);
+        memcpy(aux, h_entry_ids + i0, cnt * 8);
+        memcpy(aux + cnt, h_lacs + i0, cnt * 8);
+        memcpy(aux + 2 * cnt, h_length_fields + i0, cnt * 8);
+        if (h_ledger_ids) memcpy(aux + 3 * cnt, h_ledger_ids + i0, cnt * 8);
+        BKD_HIP(hipMemcpyAsync(hs.d_aux[s], aux, cnt * 8 * fields, hipMemcpyHostToDevice, st));
+        const int64_t* d_aux = reinterpret_cast<const int64_t*>(hs.d_aux[s]);
+        r = package_framed(*call.ds, st, algo, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
+                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], frame_stride, hs.d_res[s],
+                           h_ledger_ids ? d_aux + 3 * cnt : nullptr);
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * frame_stride, hipMemcpyDeviceToHost, st));
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy((uint8_t*)h_frames + i0 * frame_stride, hs.h_frm[s], cnt * frame_stride);
+        memcpy(h_digests + i0, hs.h_res[s], cnt * 4);
+        return BKD_OK;
+    };
+    return host_segments(hs, h_lengths, n, max_entries, seg, drain);
 }
 
 }  // namespace
@@ -1649,6 +1775,43 @@ int bkd_digest_verify_batch(int algo, int64_t ledger_id, int64_t first_entry_id,
                          d_offsets, d_lengths, n, d_status, d_first_bad);
 }
 
+int bkd_digest_package_batch_ledgers(int algo, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                     const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                     uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                                     uint64_t n, void* d_frames, uint64_t frame_stride, uint32_t* d_digests,
+                                     void* stream) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    const uint32_t mac = mac_len(algo);
+    if (n == 0) return BKD_OK;
+    if (!d_ledger_ids || !d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_frames ||
+        !d_digests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return package_framed(*call.ds, call.st, algo, 0, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
+                          d_offsets, d_lengths, n, d_frames, frame_stride, d_digests, d_ledger_ids);
+}
+
+int bkd_digest_verify_requests(int algo, const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                               const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first, uint64_t nreq,
+                               const int64_t* d_req_ledger_ids, const int64_t* d_req_first_entry_ids,
+                               const uint32_t* d_req_flags, int32_t* d_status, uint64_t* d_req_first_bad,
+                               void* stream) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if (!d_req_first || !d_req_ledger_ids || !d_req_first_entry_ids || !d_req_flags || !d_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    const Requests rq{nreq, d_req_first, d_req_ledger_ids, d_req_first_entry_ids, d_req_flags, d_req_first_bad};
+    return verify_framed(*call.ds, call.st, algo, 0, 0, 0, d_framed, framed_size, d_offsets, d_lengths, n, d_status,
+                         nullptr, &rq);
+}
+
 int bkd_digest_verify_batch_host(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check,
                                  const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
                                  int32_t* h_status, uint64_t* h_first_bad) {
@@ -1711,33 +1874,117 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   h_digests);
         return BKD_OK;
     }
-    StagedCall call(&HostStage::init_package);
+    return package_host_staged(algo, ledger_id, nullptr, h_entry_ids, h_lacs, h_length_fields, h_payloads, h_lengths, n,
+                               h_frames, frame_stride, h_digests);
+}
+
+int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                                    const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
+                                    const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags,
+                                    int32_t* h_status, uint64_t* h_req_first_bad) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if (!h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags || !h_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    // the CSR, before any work: starts at 0, never decreases, ends at n
+    if (h_req_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "req_first[0] is not 0");
+    for (uint64_t r = 0; r < nreq; ++r)
+        if (h_req_first[r + 1] < h_req_first[r])
+            return fail(BKD_ERR_INVALID_ARG, "req_first decreases at request " + std::to_string(r));
+    if (h_req_first[nreq] != n) return fail(BKD_ERR_INVALID_ARG, "req_first[nreq] is not n");
+    for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
+    if (n == 0) return BKD_OK;
+    if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
+    const int route = framed_host_route(h_lengths, n);
+    if (route < 0) return route;
+    // the requests as per-entry expectations: what the CPU route checks frame by frame and what the
+    // GPU route stages beside the frames
+    std::vector<int64_t> xlid(n), xeid(n);
+    std::vector<uint32_t> req_of(n);
+    for (uint64_t r = 0; r < nreq; ++r)
+        for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i) {
+            xlid[i] = h_req_ledger_ids[r];
+            xeid[i] = (int64_t)((uint64_t)h_req_first_entry_ids[r] + (i - h_req_first[r]));
+            req_of[i] = (uint32_t)r | ((h_req_flags[r] & 1u) ? bkd::host::kSkipEntryId : 0u);
+        }
+    // statuses come back to the host on either route: each request's verified prefix is its first
+    // non-zero status
+    auto prefixes = [&] {
+        for (uint64_t r = 0; r < nreq; ++r)
+            for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i)
+                if (h_status[i] != 0) {
+                    h_req_first_bad[r] = i - h_req_first[r];
+                    break;
+                }
+    };
+    if (route == 1) {
+        bkd::host::verify_frames_expected(algo, xlid.data(), xeid.data(), req_of.data(), (const uint8_t* const*)h_frames,
+                                          h_lengths, n, h_status);
+        prefixes();
+        return BKD_OK;
+    }
+    StagedCall call(&HostStage::init_verify, &HostStage::init_requests);
     if (call.rc) return call.rc;
     HostStage& hs = **call.lease;
-    const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / frame_stride);
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
         const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
         if (r) return r;
-        int64_t* aux = reinterpret_cast<int64_t*>(hs.h_aux[s]);
-        memcpy(aux, h_entry_ids + i0, cnt * 8);
-        memcpy(aux + cnt, h_lacs + i0, cnt * 8);
-        memcpy(aux + 2 * cnt, h_length_fields + i0, cnt * 8);
-        BKD_HIP(hipMemcpyAsync(hs.d_aux[s], aux, cnt * 24, hipMemcpyHostToDevice, st));
-        const int64_t* d_aux = reinterpret_cast<const int64_t*>(hs.d_aux[s]);
-        r = package_framed(*call.ds, st, algo, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
-                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], frame_stride, hs.d_res[s]);
+        // [ledger ids][entry ids][request 0 + skip bit][pad to 8][one zero u64: request 0's first entry]
+        const size_t o_eid = cnt * 8, o_req = cnt * 16, o_zero = (cnt * 20 + 7) & ~(size_t)7;
+        memcpy(hs.h_rq[s], xlid.data() + i0, cnt * 8);
+        memcpy(hs.h_rq[s] + o_eid, xeid.data() + i0, cnt * 8);
+        uint32_t* rq_of = reinterpret_cast<uint32_t*>(hs.h_rq[s] + o_req);
+        for (uint64_t j = 0; j < cnt; ++j) rq_of[j] = req_of[i0 + j] & bkd::host::kSkipEntryId;
+        memset(hs.h_rq[s] + cnt * 20, 0, o_zero + 8 - cnt * 20);
+        BKD_HIP(hipMemcpyAsync(hs.d_rq[s], hs.h_rq[s], o_zero + 8, hipMemcpyHostToDevice, st));
+        const uint8_t* d = hs.d_rq[s];
+        Requests rq{1, reinterpret_cast<const uint64_t*>(d + o_zero), nullptr, nullptr, nullptr, hs.d_fb[s]};
+        rq.exp_lid = reinterpret_cast<const int64_t*>(d);
+        rq.exp_eid = reinterpret_cast<const int64_t*>(d + o_eid);
+        rq.req_of = reinterpret_cast<const uint32_t*>(d + o_req);
+        r = verify_framed(*call.ds, st, algo, 0, 0, 0, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
+                          reinterpret_cast<int32_t*>(hs.d_res[s]), nullptr, &rq);
         if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * frame_stride, hipMemcpyDeviceToHost, st));
         BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
         return BKD_OK;
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy((uint8_t*)h_frames + i0 * frame_stride, hs.h_frm[s], cnt * frame_stride);
-        memcpy(h_digests + i0, hs.h_res[s], cnt * 4);
+        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
         return BKD_OK;
     };
-    return host_segments(hs, h_lengths, n, max_entries, seg, drain);
+    const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
+    if (rc == BKD_OK) prefixes();
+    return rc;
+}
+
+int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                                          const int64_t* h_lacs, const int64_t* h_length_fields,
+                                          const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
+                                          void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    const uint32_t mac = mac_len(algo);
+    if (n == 0) return BKD_OK;
+    if (!h_ledger_ids || !h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_frames ||
+        !h_digests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (frame_stride < 32u + mac || frame_stride > 4096u)
+        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+    const int route = framed_host_route(h_lengths, n);
+    if (route < 0) return route;
+    if (route == 1) {
+        bkd::host::package_frames_ledgers(algo, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                                          (const uint8_t* const*)h_payloads, h_lengths, n, (uint8_t*)h_frames,
+                                          frame_stride, h_digests);
+        return BKD_OK;
+    }
+    return package_host_staged(algo, 0, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, h_payloads, h_lengths, n,
+                               h_frames, frame_stride, h_digests);
 }
 
 int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check, uint32_t flags,

@@ -2044,4 +2044,322 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
     held.finish(g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
 }
 
+// ---- batches that span many ledgers (bkd_digest_verify_requests, bkd_digest_package_batch_ledgers) ----
+// The kernels above take one ledger id per launch. These forms take it per entry; they stand beside
+// the single-ledger kernels, whose machine code stays what it was (folding both onto one templated
+// body changed the single-ledger kernels' code: profiles/requests_kernel_disasm.txt),
+// and share their device functions (fold_range, HeldResults, mul_aux, put_frame_digest).
+
+// What request_expand_kernel writes per entry and the verify kernels read: the expected ledger id and
+// entry id and the entry's request (bit 31: the request skips the entry-id check), and where a
+// failing entry lowers its request's verified prefix: req_first_bad[r] = min(i - req_first[r]).
+constexpr uint32_t kReqSkipEntryId = 0x80000000u;
+
+struct RequestIds {
+    const int64_t* __restrict__ exp_lid;
+    const int64_t* __restrict__ exp_eid;
+    const uint32_t* __restrict__ req_of;
+    const uint64_t* __restrict__ req_first;
+    unsigned long long* req_first_bad;
+    // 0, 3 (ledger id mismatch, DigestManager.java:267-273) or 4 (entry id, :275-281) from the header's
+    // first four dwords as stored (big-endian): 32-bit halves, no 64-bit id is rebuilt
+    __device__ __forceinline__ static int32_t id_status(const uint32_t* hw, int64_t lid, int64_t eid, uint32_t req) {
+        const uint32_t dl = (hw[0] ^ __builtin_bswap32((uint32_t)((uint64_t)lid >> 32))) |
+                            (hw[1] ^ __builtin_bswap32((uint32_t)lid));
+        const uint32_t de = (hw[2] ^ __builtin_bswap32((uint32_t)((uint64_t)eid >> 32))) |
+                            (hw[3] ^ __builtin_bswap32((uint32_t)eid));
+        return dl ? 3 : ((de && !(req & kReqSkipEntryId)) ? 4 : 0);
+    }
+    __device__ __forceinline__ void failed(uint32_t req, uint64_t i) const {
+        const uint32_t r = req & ~kReqSkipEntryId;
+        atomicMin(req_first_bad + r, (unsigned long long)(i - req_first[r]));
+    }
+};
+
+// The CSR of bkd_digest_verify_requests into per-entry expectations. One thread per entry, a binary
+// search over req_first for the entry's request (the last r with req_first[r] <= i): the same code
+// serves one request (no step), one entry per request and many empty requests (which no entry lands
+// on), and a thread's work is log2(nreq) reads of an array that stays in L2 — a wave per request would
+// idle 63 lanes at one entry per request and walk 3n requests for n entries. The same grid-stride
+// threads, indexed by request, check the CSR (req_first[0] == 0, non-decreasing, req_first[nreq] == n;
+// a violation raises the stream's bounds flag) and set req_first_bad[r] to the request's entry count.
+// The search stays inside [0, nreq) and nothing is indexed by a value read from req_first, so a
+// malformed CSR gives unspecified outputs, never an access outside the arrays.
+__global__ void __launch_bounds__(256) request_expand_kernel(
+    const uint64_t* __restrict__ req_first, uint64_t nreq, uint64_t n, const int64_t* __restrict__ req_ledger_ids,
+    const int64_t* __restrict__ req_first_entry_ids, const uint32_t* __restrict__ req_flags,
+    int64_t* __restrict__ exp_lid, int64_t* __restrict__ exp_eid, uint32_t* __restrict__ req_of,
+    unsigned long long* __restrict__ req_first_bad, uint32_t* __restrict__ err) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t r = t0; r < nreq; r += stride) {
+        const uint64_t a = req_first[r], b = req_first[r + 1];
+        const bool bad = b < a || (r == 0 && a != 0u) || (r == nreq - 1 && b != n);
+        if (bad) atomicOr(err, 1u);
+        req_first_bad[r] = bad ? 0ull : b - a;
+    }
+    for (uint64_t i = t0; i < n; i += stride) {
+        uint64_t lo = 0, hi = nreq;  // the last r in [0, nreq) with req_first[r] <= i (0 if none)
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (req_first[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        exp_lid[i] = req_ledger_ids[lo];
+        exp_eid[i] = (int64_t)((uint64_t)req_first_entry_ids[lo] + (i - req_first[lo]));
+        req_of[i] = (uint32_t)lo | ((req_flags[lo] & 1u) ? kReqSkipEntryId : 0u);
+    }
+}
+
+// crc_verify_fused_kernel's loop with per-entry expectations: their three loads leave with
+// offsets[i] / lengths[i], in flight with the header read; the ids are compared when the header
+// dwords arrive, so one status code is held across the payload fold, not two 64-bit ids; and a
+// failing entry lowers its request's prefix word (lane 0, on failure only).
+template <int G, int PF, bool NT>
+__global__ void __launch_bounds__(kBlock) crc_verify_fused_requests_kernel(
+    const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
+    const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, RequestIds ids,
+    const uint32_t* __restrict__ tables, int32_t* __restrict__ status, const uint32_t* __restrict__ vflag,
+    uint32_t vepoch, int sched) {
+    using Gm = Geo<G>;
+    if (*vflag == vepoch) return;  // some frame out of band: the header / plan / finish sequence runs
+    __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
+    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
+    const int lane = threadIdx.x & 63;
+    const int g = lane & (G - 1);
+    const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
+    const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
+    const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
+    HeldResults<G, kHoldStore> held;
+    for (uint64_t i = gid; i < n; i += ngroups) {
+        const uint64_t o = offsets[i];
+        const uint32_t l = lengths[i];
+        const int64_t xl = ids.exp_lid[i], xe = ids.exp_eid[i];
+        const uint32_t req = ids.req_of[i];
+        int32_t st;
+        if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
+            st = 1;  // VERIFY_TOO_SHORT (verify_header_kernel's rule for frames outside the buffer too)
+        } else {
+            const uint8_t* f = base + o;
+            const u32x4 h0 = ld16<false>(f), h1 = ld16<false>(f + 16);
+            const uint32_t hw[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+            uint32_t reg = 0xFFFFFFFFu;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) reg = mul_aux(lds, Gm::kX32Off, reg ^ hw[k]);
+            const int32_t idst = RequestIds::id_status(hw, xl, xe, req);
+            const int64_t s = (int64_t)(o + 32u + mac), e = (int64_t)(o + l);
+            uint32_t v;
+            if (e - s < 16) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
+                v = reg;
+                for (const uint8_t* q = base + s; q < base + e; ++q)
+                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
+            } else {
+                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, reg)
+                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, reg);
+            }
+            const uint32_t computed = ~v;
+            // digest: 4-byte BE int (CRC32C) or 8-byte BE zero-extended long (CRC32) at offset 32
+            uint32_t expect, hi = 0u;
+            if (mac == 8u) {
+                hi = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 32));
+                expect = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 36));
+            } else {
+                expect = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 32));
+            }
+            // DigestManager.verifyDigest's order (DigestManager.java:226-283): digest, ledger id, entry id
+            st = (hi != 0u || computed != expect) ? 2 : idst;
+        }
+        held.put((uint32_t)st, g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
+        if (g == 0 && st != 0) ids.failed(req, i);
+    }
+    held.finish(g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
+}
+
+// verify_header_kernel with the id checks read from the expanded arrays (and no first_bad word to
+// set: the per-request prefixes are request_expand_kernel's to initialise).
+__global__ void __launch_bounds__(1024) verify_header_requests_kernel(
+    const uint32_t* __restrict__ x32tab, const uint8_t* __restrict__ framed, uint64_t size,
+    const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, RequestIds ids,
+    uint32_t* __restrict__ seeds, uint64_t* __restrict__ pay_offsets, uint32_t* __restrict__ pay_lengths,
+    uint32_t* __restrict__ expect, uint32_t* __restrict__ pre, const uint32_t* __restrict__ vflag, uint32_t vepoch) {
+    if (vflag && *vflag != vepoch) return;  // near-uniform frames: crc_verify_fused_requests_kernel does it all
+    __shared__ uint32_t W[1024];
+    for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t o = offsets[i];
+        const uint32_t l = lengths[i];
+        if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
+            seeds[i] = 0u;
+            pay_offsets[i] = 0u;
+            pay_lengths[i] = 0u;
+            expect[i] = 0u;
+            pre[i] = 1u;
+            continue;
+        }
+        uint32_t w[10];
+        load_frame_head(framed + o, l, mac, w);
+        uint32_t reg = 0xFFFFFFFFu;  // update(0, header): resume from 0 = register ~0
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t r = reg ^ w[k];
+            reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
+        }
+        seeds[i] = ~reg;
+        pay_offsets[i] = o + 32u + mac;
+        pay_lengths[i] = l - 32u - mac;
+        uint32_t p = (mac == 8u && w[8] != 0u) ? 2u : 0u;
+        expect[i] = __builtin_bswap32(mac == 8u ? w[9] : w[8]);
+        p |= (uint32_t)RequestIds::id_status(w, ids.exp_lid[i], ids.exp_eid[i], ids.req_of[i]) << 2;
+        pre[i] = p;
+    }
+}
+
+// verify_finish_kernel with the verified prefix per request.
+__global__ void __launch_bounds__(256) verify_finish_requests_kernel(const uint32_t* __restrict__ expect,
+                                                                     const uint32_t* __restrict__ pre, uint64_t n,
+                                                                     int32_t* __restrict__ status, RequestIds ids,
+                                                                     const uint32_t* __restrict__ vflag,
+                                                                     uint32_t vepoch) {
+    if (vflag && *vflag != vepoch) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t computed = (uint32_t)status[i];
+    const uint32_t p = pre[i];
+    int32_t st;
+    if (p == 1u) st = 1;
+    else if ((p & 2u) || computed != expect[i]) st = 2;
+    else st = (int32_t)(p >> 2);
+    status[i] = st;
+    if (st != 0) ids.failed(ids.req_of[i], i);
+}
+
+// The 32-byte header [ledgerId, entryId, LAC, length] (DigestManager.java:146-149) as the 8
+// little-endian dwords that hold its big-endian fields.
+__device__ __forceinline__ void header_dwords(int64_t ledger_id, int64_t entry_id, int64_t lac, int64_t length,
+                                              uint32_t* w) {
+    const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_id, (uint64_t)lac, (uint64_t)length};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
+        w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
+    }
+}
+
+// package_header_kernel with ledger_ids[i] read beside entry_ids[i].
+__global__ void __launch_bounds__(1024) package_header_ledgers_kernel(
+    const uint32_t* __restrict__ x32tab, const int64_t* __restrict__ ledger_ids, const int64_t* __restrict__ entry_ids,
+    const int64_t* __restrict__ lacs, const int64_t* __restrict__ length_fields, uint64_t n, uint8_t* __restrict__ frames,
+    uint64_t frame_stride, uint32_t* __restrict__ seeds) {
+    __shared__ uint32_t W[1024];
+    for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t w[8];
+        header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
+        uint32_t reg = 0xFFFFFFFFu;  // update(0, header)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t r = reg ^ w[k];
+            reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
+        }
+        uint8_t* f = frames + i * frame_stride;
+        if ((((uintptr_t)f) & 3u) == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
+        } else {
+            for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        }
+        seeds[i] = ~reg;
+    }
+}
+
+// package_frame_kernel with ledger_ids[i]: the packed LDS path and the per-thread path.
+__global__ void __launch_bounds__(256) package_frame_ledgers_kernel(
+    const int64_t* __restrict__ ledger_ids, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
+    const int64_t* __restrict__ length_fields, const uint32_t* __restrict__ digests, uint64_t n,
+    uint8_t* __restrict__ frames, uint64_t frame_stride, uint32_t mac) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (frame_stride == 32u + mac && (((uintptr_t)frames) & 3u) == 0) {
+        __shared__ uint32_t fr[256 * 10];
+        const uint32_t fw = (32u + mac) / 4u;  // dwords per frame
+        const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x;
+        const uint32_t cnt = (uint32_t)(n - i0 < (uint64_t)blockDim.x ? n - i0 : (uint64_t)blockDim.x);
+        if (i < n) {
+            uint32_t* w = fr + threadIdx.x * fw;
+            header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
+            if (mac == 8u) w[8] = 0u;
+            w[fw - 1u] = __builtin_bswap32(digests[i]);
+        }
+        __syncthreads();
+        uint32_t* dst = reinterpret_cast<uint32_t*>(frames + i0 * frame_stride);
+        for (uint32_t k = threadIdx.x; k < cnt * fw; k += blockDim.x) dst[k] = fr[k];
+        return;
+    }
+    if (i >= n) return;
+    const uint32_t dg = digests[i];
+    uint32_t w[8];
+    header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
+    uint8_t* f = frames + i * frame_stride;
+    if ((((uintptr_t)f) & 3u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
+    } else {
+        for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+    put_frame_digest(f + 32, dg, mac);
+}
+
+// crc_package_fused_kernel with ledger_ids[i]: one more per-group load beside entry_ids[i], in flight
+// with the payload's first loads (the header register is a late seed, as there).
+template <int G, int PF, bool NT>
+__global__ void __launch_bounds__(kBlock) crc_package_fused_ledgers_kernel(
+    const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
+    const uint32_t* __restrict__ lengths, uint64_t n, const int64_t* __restrict__ ledger_ids,
+    const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs, const int64_t* __restrict__ length_fields,
+    const uint32_t* __restrict__ tables, uint32_t* __restrict__ digests, uint32_t* __restrict__ err, int sched) {
+    using Gm = Geo<G>;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
+    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
+    const int lane = threadIdx.x & 63;
+    const int g = lane & (G - 1);
+    const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
+    const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
+    const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
+    HeldResults<G, kHoldStore> held;
+    for (uint64_t i = gid; i < n; i += ngroups) {
+        const uint64_t o = offsets[i];
+        const uint32_t l = lengths[i];
+        uint32_t hw[8];
+        header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], hw);
+        uint32_t d;
+        if (o > size || (uint64_t)l > size - o) {
+            d = 0u;
+            if (g == 0 && err) atomicOr(err, 1u);
+        } else {
+            // update(0, header), evaluated by fold_range after the payload's first loads are issued
+            auto header_reg = [&]() {
+                uint32_t reg = 0xFFFFFFFFu;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) reg = mul_aux(lds, Gm::kX32Off, reg ^ hw[k]);
+                return reg;
+            };
+            uint32_t v;
+            if (l < 16u) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
+                v = header_reg();
+                for (const uint8_t* q = base + o; q < base + o + l; ++q)
+                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
+            } else {
+                const int64_t s = (int64_t)o, e = s + (int64_t)l;
+                const LateSeed<decltype(header_reg)> late{header_reg};
+                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, late)
+                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, late);
+            }
+            d = ~v;
+        }
+        held.put(d, g, digests, gid, ngroups, n);
+    }
+    held.finish(g, digests, gid, ngroups, n);
+}
+
 }  // namespace bkd

@@ -251,6 +251,43 @@ inline uint32_t reframed_digest(int algo, uint32_t mac, const uint8_t* f, uint32
     return be32(f + 32 + (mac - 4u)) ^ delta;
 }
 
+// verify_frames / verify_frames_expected: expected(i, &ledger_id, &entry_id) -> id_checks of frame i.
+template <class Expected>
+uint64_t verify_frames_by(int algo, Expected&& expected, const uint8_t* const* frames, const uint32_t* lens, uint64_t n,
+                          int32_t* status) {
+    const uint32_t mac = mac_len(algo);
+    return walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
+        int64_t lid, eid;
+        const int id_checks = expected(i, &lid, &eid);
+        return status[i] = frame_status(algo, mac, lid, eid, id_checks, frames[i], lens[i], whole_pool, true);
+    });
+}
+
+// package_frames / package_frames_ledgers: ledger(i) = the ledger id that frames entry i.
+// DigestManager.computeDigestAndPackageForSending (:117-181): header [ledgerId, entryId, LAC, length]
+// BE (:146-149), digest = update(update(0, header), payload) (:152-153), written after the header
+// (CRC32CDigestManager.java:44-46 writeInt; CRC32DigestManager.java:60-63 writeLong, zero-extended).
+template <class Ledger>
+void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, const int64_t* lacs,
+                       const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
+                       uint8_t* frames, uint64_t stride, uint32_t* digests) {
+    const uint32_t mac = mac_len(algo);
+    walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
+        uint8_t* f = frames + i * stride;
+        put_be64(f, (uint64_t)ledger(i));
+        put_be64(f + 8, (uint64_t)entry_ids[i]);
+        put_be64(f + 16, (uint64_t)lacs[i]);
+        put_be64(f + 24, (uint64_t)length_fields[i]);
+        uint32_t reg = crc_raw(algo, 0xFFFFFFFFu, f, 32);
+        if (lens[i]) reg = whole_pool ? fold(algo, reg, payloads[i], lens[i]) : crc_raw(algo, reg, payloads[i], lens[i]);
+        const uint32_t d = ~reg;
+        if (mac == 8u) put_be32(f + 32, 0u);
+        put_be32(f + 32 + (mac - 4u), d);
+        digests[i] = d;
+        return 0;
+    });
+}
+
 }  // namespace
 
 uint32_t fold(int algo, uint32_t reg, const uint8_t* p, uint64_t len) {
@@ -290,34 +327,34 @@ void crc_indexed(int algo, const uint8_t* base, const uint64_t* offsets, const u
 // DigestManager.verifyDigest per frame (frame_status).
 uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks,
                        const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
-    const uint32_t mac = mac_len(algo);
-    return walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
-        return status[i] = frame_status(algo, mac, ledger_id, first_entry_id + (int64_t)i, id_checks, frames[i], lens[i],
-                                        whole_pool, true);
-    });
+    return verify_frames_by(algo, [&](uint64_t i, int64_t* lid, int64_t* eid) {
+        *lid = ledger_id;
+        *eid = first_entry_id + (int64_t)i;
+        return id_checks;
+    }, frames, lens, n, status);
 }
 
-// DigestManager.computeDigestAndPackageForSending (:117-181): header [ledgerId, entryId, LAC, length]
-// BE (:146-149), digest = update(update(0, header), payload) (:152-153), written after the header
-// (CRC32CDigestManager.java:44-46 writeInt; CRC32DigestManager.java:60-63 writeLong, zero-extended).
+void verify_frames_expected(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const uint32_t* req_of,
+                            const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
+    verify_frames_by(algo, [&](uint64_t i, int64_t* lid, int64_t* eid) {
+        *lid = ledger_ids[i];
+        *eid = entry_ids[i];
+        return (req_of[i] & kSkipEntryId) ? 1 : 0;
+    }, frames, lens, n, status);
+}
+
 void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                     const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
                     uint8_t* frames, uint64_t stride, uint32_t* digests) {
-    const uint32_t mac = mac_len(algo);
-    walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
-        uint8_t* f = frames + i * stride;
-        put_be64(f, (uint64_t)ledger_id);
-        put_be64(f + 8, (uint64_t)entry_ids[i]);
-        put_be64(f + 16, (uint64_t)lacs[i]);
-        put_be64(f + 24, (uint64_t)length_fields[i]);
-        uint32_t reg = crc_raw(algo, 0xFFFFFFFFu, f, 32);
-        if (lens[i]) reg = whole_pool ? fold(algo, reg, payloads[i], lens[i]) : crc_raw(algo, reg, payloads[i], lens[i]);
-        const uint32_t d = ~reg;
-        if (mac == 8u) put_be32(f + 32, 0u);
-        put_be32(f + 32 + (mac - 4u), d);
-        digests[i] = d;
-        return 0;
-    });
+    package_frames_by(algo, [&](uint64_t) { return ledger_id; }, entry_ids, lacs, length_fields, payloads, lens, n, frames,
+                      stride, digests);
+}
+
+void package_frames_ledgers(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                            const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                            uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests) {
+    package_frames_by(algo, [&](uint64_t i) { return ledger_ids[i]; }, entry_ids, lacs, length_fields, payloads, lens, n,
+                      frames, stride, digests);
 }
 
 // LedgerFragmentReplicator's second framing of an entry it has read and verified

@@ -66,11 +66,21 @@ void crc_indexed(int algo, const uint8_t* base, const uint64_t* offsets, const u
 // 0 ledger + entry ids, 1 ledger id only. Returns the first failing index (n when all verified).
 uint64_t verify_frames(int algo, int64_t ledger_id, int64_t first_entry_id, int id_checks,
                        const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status);
+// The same with per-entry expectations (bkd_digest_verify_requests_host, its requests expanded by the
+// caller): frame i against ledger_ids[i] and entry_ids[i]; req_of[i] bit 31 (kSkipEntryId) = the
+// frame's request skips the entry-id check, the low bits its request (not read here).
+constexpr uint32_t kSkipEntryId = 0x80000000u;
+void verify_frames_expected(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const uint32_t* req_of,
+                            const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status);
 // DigestManager.computeDigestAndPackageForSending per entry (DigestManager.java:117-181): the 32-byte
 // BE header and the digest into frames + i*stride, the digest value into digests[i].
 void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                     const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
                     uint8_t* frames, uint64_t stride, uint32_t* digests);
+// The same with ledger_ids[i] framing entry i (bkd_digest_package_batch_ledgers_host).
+void package_frames_ledgers(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                            const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                            uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests);
 // Re-frames verified frames in place with new LACs (LedgerFragmentReplicator.java:436-442): status as
 // verify_frames (trusted: from the header alone, no payload byte read); a frame that is OK gets
 // new_lacs[i] at bytes 16..23 and the digest old ^ R(LAC difference) * x^(8 * payload length); the

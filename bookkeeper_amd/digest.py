@@ -309,6 +309,139 @@ class DigestManager:
         return status, int(first_bad.value), digests
 
 
+# ---- batches that span many ledgers (module level: a DigestManager is bound to one ledger) ----
+# An aggregation queue across pending reads and adds forms its batches across
+# ledgers: a few entries from each of thousands. One digest type per call, as everywhere else.
+
+def _algo_of(digest_type) -> int:
+    if digest_type in (DigestType.CRC32C, DigestType.CRC32):
+        return CRC32C if digest_type == DigestType.CRC32C else CRC32
+    if isinstance(digest_type, int) and not isinstance(digest_type, enum.Enum) and digest_type in (CRC32C, CRC32):
+        return digest_type
+    raise ValueError(f"the batch engine computes CRC32C and CRC32 digests, not {digest_type}")
+
+
+def _mac_of(algo: int) -> int:
+    return 4 if algo == CRC32C else 8
+
+
+def _check_csr_sizes(nreq: int, *arrays) -> None:
+    if any(a is not None and a != nreq for a in arrays):
+        raise ValueError("ledger_ids, first_entry_ids and skip_flags must have one element per request "
+                         "(req_first one more)")
+
+
+def verify_requests(digest_type, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags=None,
+                    stream=None):
+    """Verifies n framed device-resident entries grouped into read requests of different ledgers in one
+    launch sequence (bkd_digest_verify_requests). Request r owns entries [req_first[r], req_first[r+1])
+    (int64[nreq + 1], non-decreasing, from 0 to n; empty requests are legal), is read from ledger
+    ledger_ids[r] and expects entry ids first_entry_ids[r], first_entry_ids[r] + 1, ...; skip_flags[r]
+    bit 0 skips its entry-id check. Returns (status int32[n], req_first_bad int64[nreq]): request r's
+    entries [0, req_first_bad[r]) verified — BatchedReadOp's verified prefix per request. A malformed
+    req_first raises BKD_ERR_BOUNDS from the stream's next ``stream_sync``."""
+    import torch
+    algo = _algo_of(digest_type)
+    n = offsets.numel()
+    dev = framed.device
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    if req_first.numel() < 1:
+        raise ValueError("req_first holds nreq + 1 values")
+    nreq = req_first.numel() - 1
+    _check_csr_sizes(nreq, ledger_ids.numel(), first_entry_ids.numel(),
+                     None if skip_flags is None else skip_flags.numel())
+    if skip_flags is None:
+        skip_flags = torch.zeros(nreq, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    req_first_bad = torch.empty(nreq, dtype=torch.int64, device=dev)
+    with _ck._on_device(framed):
+        check(lib().bkd_digest_verify_requests(
+            algo, _ck._dev_ptr(framed, "framed"), framed.numel() * framed.element_size(),
+            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
+            _ck._dev_ptr(req_first, "req_first", i64, dev), nreq, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev),
+            _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev), _ck._dev_ptr(skip_flags, "skip_flags", u32, dev),
+            _ck._dev_ptr(status, "status"), _ck._dev_ptr(req_first_bad, "req_first_bad"),
+            _ck._stream_ptr(stream, framed)))
+    return status, req_first_bad
+
+
+def package_batch_ledgers(digest_type, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
+                          frame_stride=None, stream=None, sync_check: bool = False):
+    """``DigestManager.package_batch`` with ledger_ids[i] (int64[n]) framing entry i: returns
+    (frames[n, frame_stride] uint8, digests int32[n])."""
+    import torch
+    algo = _algo_of(digest_type)
+    n = offsets.numel()
+    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
+    dev = payload.device
+    frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    digests = torch.empty(n, dtype=torch.int32, device=dev)
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(lib().bkd_digest_package_batch_ledgers(
+            algo, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
+            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
+            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
+            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
+            _ck._dev_ptr(frames, "frames"), stride, _ck._dev_ptr(digests, "digests"), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+    return frames, digests
+
+
+def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry_ids, skip_flags=None):
+    """``verify_requests`` for entries in host memory: `frames` is a sequence of host buffers, each one
+    framed entry; the request arrays are host sequences. A malformed req_first raises
+    BKD_ERR_INVALID_ARG before any work. Returns (status int32[n], req_first_bad uint64[nreq])."""
+    algo = _algo_of(digest_type)
+    views = [_ck._host_view(f) for f in frames]
+    n = len(views)
+    first = np.ascontiguousarray(req_first, dtype=np.uint64)
+    if first.size < 1:
+        raise ValueError("req_first holds nreq + 1 values")
+    nreq = first.size - 1
+    lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    eids = np.ascontiguousarray(first_entry_ids, dtype=np.int64)
+    flags = np.zeros(nreq, dtype=np.uint32) if skip_flags is None else np.ascontiguousarray(skip_flags, dtype=np.uint32)
+    _check_csr_sizes(nreq, lids.size, eids.size, flags.size)
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    first_bad = np.zeros(nreq, dtype=np.uint64)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_verify_requests_host(
+        algo, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first.ctypes.data), nreq, vp(lids.ctypes.data),
+        vp(eids.ctypes.data), vp(flags.ctypes.data), vp(status.ctypes.data), vp(first_bad.ctypes.data)))
+    del views
+    return status, first_bad
+
+
+def package_batch_ledgers_host(digest_type, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride=None):
+    """``DigestManager.package_batch_host`` with ledger_ids[i] framing entry i: returns
+    (headers uint8[n, frame_stride] = [32 B header][digest], digests uint32[n])."""
+    algo = _algo_of(digest_type)
+    views = [_ck._host_view(p) for p in payloads]
+    n = len(views)
+    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
+    lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
+    lac = np.ascontiguousarray(lacs, dtype=np.int64)
+    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
+    if not (lids.size == ids.size == lac.size == lf.size == n):
+        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    frames = np.zeros((n, stride), dtype=np.uint8)
+    digests = np.zeros(n, dtype=np.uint32)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_package_batch_ledgers_host(
+        algo, vp(lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data), vp(lf.ctypes.data), vp(ptrs.ctypes.data),
+        vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
+    del views
+    return frames, digests
+
+
 class CRC32CDigestManager(DigestManager):
     """CRC32CDigestManager.java:27-62."""
     algo = CRC32C

@@ -232,6 +232,52 @@ BKD_API int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int
                                           const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
                                           void* h_frames, uint64_t frame_stride, uint32_t* h_digests);
 
+/* ---- batches that span many ledgers (an aggregation queue across pending adds and reads) ----
+ * The calls above are bound to one ledger: one BatchedReadOp ($BK/client/BatchedReadOp.java:164-190)
+ * or one ledger's adds ($BK/client/PendingAddOp.java:261). A client that serves thousands of open
+ * ledgers has a few reads or adds outstanding on each and can only form large batches ACROSS ledgers
+ * (SURVEY.md §8f rank 2); these calls take such a batch whole, one launch sequence for all of it.
+ *
+ * Verify: entries are the framed buffers of bkd_digest_verify_batch, grouped into nreq read requests
+ * in CSR form: request r owns entries [d_req_first[r], d_req_first[r+1]). d_req_first holds nreq + 1
+ * non-decreasing values, d_req_first[0] == 0 and d_req_first[nreq] == n; empty requests are legal
+ * anywhere. Entry i of request r is verified exactly as DigestManager.verifyDigest does
+ * ($BK/proto/checksum/DigestManager.java:226-283) with ledger id d_req_ledger_ids[r] and expected entry
+ * id d_req_first_entry_ids[r] + (i - d_req_first[r]); d_req_flags[r] bit 0 skips the entry-id check
+ * (skipEntryIdCheck, DigestManager.java:206-208). d_status[i]: the BKD_VERIFY_* code, same precedence
+ * (too short, digest, ledger, entry). d_req_first_bad[r]: the index WITHIN request r of its first
+ * failing entry, or the request's entry count if none failed — BatchedReadOp's verified prefix, per
+ * request. n == 0 writes zeros to d_req_first_bad. nreq < 2^31; nreq == 0 requires n == 0.
+ * Device pointers; asynchronous on `stream`; no host synchronisation. A malformed CSR is detected on
+ * the device: it raises the stream's bounds flag (BKD_ERR_BOUNDS from the next bkd_stream_sync), never
+ * causes an access outside the caller's arrays, and leaves the outputs unspecified. */
+#define BKD_REQUEST_SKIP_ENTRY_ID 1u /* d_req_flags bit 0 */
+BKD_API int bkd_digest_verify_requests(int algo, const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                                       const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first,
+                                       uint64_t nreq, const int64_t* d_req_ledger_ids,
+                                       const int64_t* d_req_first_entry_ids, const uint32_t* d_req_flags,
+                                       int32_t* d_status, uint64_t* d_req_first_bad, void* stream);
+/* Package: bkd_digest_package_batch with d_ledger_ids[i] framing entry i in place of the one ledger_id
+ * (DigestManager.java:146-149); routes, d_digests and bounds reporting are the same. */
+BKD_API int bkd_digest_package_batch_ledgers(int algo, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                             const int64_t* d_lacs, const int64_t* d_length_fields,
+                                             const void* d_payload, uint64_t payload_size, const uint64_t* d_offsets,
+                                             const uint32_t* d_lengths, uint64_t n, void* d_frames,
+                                             uint64_t frame_stride, uint32_t* d_digests, void* stream);
+/* Host-resident forms: buffers as bkd_digest_verify_batch_host / bkd_digest_package_batch_host, the
+ * request arrays / ledger ids in host memory; route by bkd_set_host_batch_route. The CSR is validated
+ * before any work (BKD_ERR_INVALID_ARG). Synchronous. */
+BKD_API int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const uint32_t* h_lengths,
+                                            uint64_t n, const uint64_t* h_req_first, uint64_t nreq,
+                                            const int64_t* h_req_ledger_ids, const int64_t* h_req_first_entry_ids,
+                                            const uint32_t* h_req_flags, int32_t* h_status,
+                                            uint64_t* h_req_first_bad);
+BKD_API int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                                                  const int64_t* h_lacs, const int64_t* h_length_fields,
+                                                  const void* const* h_payloads, const uint32_t* h_lengths,
+                                                  uint64_t n, void* h_frames, uint64_t frame_stride,
+                                                  uint32_t* h_digests);
+
 /* ---- re-framing verified entries with a new LAC (re-replication) -----------------------
  * LedgerFragmentReplicator frames every entry it has just read and verified a second time with the
  * ledger's current LAC: computeDigestAndPackageForSending(entryId, lh.getLastAddConfirmed(),
