@@ -81,6 +81,13 @@ PROTOTYPES = {
                                                 _vp]),
     "bkd_digest_verify_requests_host": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "bkd_digest_package_batch_ledgers_host": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "bkd_digest_package_batch_segments": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64,
+                                                 _vp, _u64, _vp, _vp]),
+    "bkd_digest_package_batch_segments_host": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,
+                                                      _u64, _vp]),
+    "bkd_crc_batch_segments_host": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _u32, _vp]),
+    "bkd_host_segment_bytewise": (_int, [_u64, _u32, _u64]),
+    "bkd_host_segments_range": (_int, [_u64, _u64, _u64, _u64, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),
     "bkd_digest_reframe_batch": (_int, [_int, _i64, _i64, _int, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
                                         _vp, _vp, _vp]),
     "bkd_digest_reframe_batch_host": (_int, [_int, _i64, _i64, _int, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),

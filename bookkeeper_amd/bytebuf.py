@@ -9,7 +9,9 @@ over them, so the digest equals the digest of the concatenated bytes without cop
 ``CompositeBuffer`` is the host-side stand-in for those Netty buffers (components = bytes-like objects
 or other composites; ``reader_index`` / ``writer_index`` / ``slice`` / ``duplicate`` as in Netty), and
 ``visit`` yields the same leaf ranges. On the device, entries made of several segments go through
-``checksum.crc_batch_segments`` (``bkd_crc_batch_segments``) instead.
+``checksum.crc_batch_segments`` (``bkd_crc_batch_segments``) instead, and batches of composite adds are
+framed by ``DigestManager.package_batch_segments`` / ``package_batch_segments_host``, which take a
+``CompositeBuffer`` per payload and pass its leaves on without joining them.
 """
 from __future__ import annotations
 

@@ -31,7 +31,7 @@ from . import _native
 from ._native import CRC32, CRC32C, check, lib
 
 __all__ = ["CRC32C", "CRC32", "GpuIntHash", "Crc32cIntChecksum", "crc_batch", "crc_batch_uniform",
-           "crc_batch_segments", "crc_batch_host", "release_stream", "cpu_resume", "set_cpu_route_max", "to_java_int"]
+           "crc_batch_segments", "crc_batch_host", "crc_batch_segments_host", "release_stream", "cpu_resume", "set_cpu_route_max", "to_java_int"]
 
 
 def to_java_int(v: int) -> int:
@@ -277,6 +277,43 @@ def crc_batch_host(algo: int, base, offsets, lengths, seeds=None, seed_all: int 
     return out
 
 
+def _host_segments(segments, seg_first):
+    """(views, pointers uint64[nseg], lengths uint32[nseg], seg_first uint64[n + 1], n) of host segments
+    in CSR form, the sizes checked; the views keep the buffers alive across the call."""
+    views = [_host_view(s) for s in segments]
+    first = np.ascontiguousarray(seg_first, dtype=np.uint64)
+    if first.ndim != 1 or first.size < 1:
+        raise ValueError("seg_first holds n + 1 values")
+    if any(v.size >= 2**32 for v in views):
+        raise ValueError("a segment holds fewer than 2^32 bytes")
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    return views, ptrs, lens, first, first.size - 1
+
+
+def crc_batch_segments_host(algo: int, segments, seg_first, seeds=None, seed_all: int = 0) -> np.ndarray:
+    """``crc_batch_segments`` for segments in host memory (bkd_crc_batch_segments_host): `segments` is a
+    sequence of host buffers, entry i the concatenation of segments seg_first[i] .. seg_first[i+1]-1
+    (n + 1 values from 0 to len(segments)); returns uint32 out[i] = resume(seed_i, concatenation). A
+    malformed seg_first raises BKD_ERR_INVALID_ARG before any work. Route as
+    ``DigestManager.package_batch_segments_host``: the CPU threads or the GPU by ``set_host_batch_route``; an entry
+    whose segments sum to more than 64 MiB takes the CPU route, or raises BKD_ERR_INVALID_ARG when the GPU route is
+    forced."""
+    views, ptrs, lens, first, n = _host_segments(segments, seg_first)
+    out = np.zeros(n, dtype=np.uint32)
+    vp = ctypes.c_void_p
+    sp = vp(0)
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if seeds.size < n:
+            raise ValueError(f"seeds has {seeds.size} elements, needs {n}")
+        sp = vp(seeds.ctypes.data)
+    check(lib().bkd_crc_batch_segments_host(algo, vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views),
+                                            vp(first.ctypes.data), n, sp, seed_all & 0xFFFFFFFF, vp(out.ctypes.data)))
+    del views
+    return out
+
+
 def fill_splitmix64(buf, seed: int, first_word: int = 0, stream=None) -> None:
     """Device-side synthetic input: little-endian splitmix64 words."""
     nbytes = buf.numel() * buf.element_size()
@@ -383,9 +420,25 @@ def set_fold_schedule(schedule: int) -> None:
     check(lib().bkd_set_fold_schedule(schedule))
 
 
+_plan_mode = 0  # the mode last set through this module (the library's default is automatic)
+
+
 def set_plan_mode(mode: int) -> None:
     """0 = auto, 1 = one entry per lane group, 2 = chunked plan (indexed batches)."""
+    global _plan_mode
     check(lib().bkd_set_plan_mode(mode))
+    _plan_mode = mode
+
+
+@contextlib.contextmanager
+def plan_mode(mode: int):
+    """Temporarily force the indexed-batch strategy (tests, tools); restores the previous one."""
+    prev = _plan_mode
+    set_plan_mode(mode)
+    try:
+        yield
+    finally:
+        set_plan_mode(prev)
 
 
 def set_plan_small(max_bytes: int = 192) -> None:

@@ -561,6 +561,10 @@ hipMemoryType pointer_type(const void* p, int* dev = nullptr) {
 struct HostStage {
     static constexpr size_t kSeg = 64u << 20;
     static constexpr size_t kSegEntries = 1u << 20;
+    // d_buf holds kSeg staged bytes and this much more: the indexed kernels load whole 16-byte blocks (an
+    // entry shorter than 16 bytes, an empty one included, the block at offset & ~15), which for an entry
+    // at the very end of a full segment must still lie inside the allocation
+    static constexpr size_t kSegSlack = 256;
     bool ready = false;
     uint8_t *h_pin[2] = {}, *d_buf[2] = {};
     uint64_t *h_off[2] = {}, *d_off[2] = {};
@@ -606,7 +610,7 @@ struct HostStage {
     int init() {
         if (ready) return BKD_OK;
         for (int s = 0, rc; s < 2; ++s) {
-            if ((rc = pin(h_pin[s], kSeg)) || (rc = dev(d_buf[s], kSeg)) ||
+            if ((rc = pin(h_pin[s], kSeg)) || (rc = dev(d_buf[s], kSeg + kSegSlack)) ||
                 (rc = pin(h_off[s], kSegEntries * 8)) || (rc = dev(d_off[s], kSegEntries * 8)) ||
                 (rc = pin(h_len[s], kSegEntries * 4)) || (rc = dev(d_len[s], kSegEntries * 4)) ||
                 (rc = pin(h_seed[s], kSegEntries * 4)) || (rc = dev(d_seed[s], kSegEntries * 4)) ||
@@ -977,6 +981,71 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     return BKD_OK;
 }
 
+// Package with composite payloads (bkd_digest_package_batch_segments): every segment's zero-initialised
+// register through the indexed path (seed ~0, as bkd_crc_batch_segments; direct kernel or chunked plan,
+// out-of-range segments skipped and flagged there) -> package_segments_join_kernel (header fold, then
+// the entry's segments joined with the byte-power table; the CSR clamped and checked) -> the frame
+// writer of the fused package route. Each payload byte is read once and none is copied; no host sync.
+// On the plan route one launch goes in front (segments_for_plan_kernel): the plan's short-entry launch
+// loads whole 16-byte blocks for entries under 16 bytes, so those segments are handed to it as (0, 0)
+// from the stream's scratch and the join kernel folds their bytes itself. No segment, wherever it lies
+// in the payload, then makes the call read a byte outside [d_payload, d_payload + payload_size) but the
+// plan's aligned lines around segments of 16 bytes and more, as for every indexed batch.
+int package_segments(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_ledger_ids,
+                     const int64_t* d_entry_ids, const int64_t* d_lacs, const int64_t* d_length_fields,
+                     const void* d_payload, uint64_t payload_size, const uint64_t* d_seg_offsets,
+                     const uint32_t* d_seg_lengths, uint64_t nseg, const uint64_t* d_seg_first, uint64_t n,
+                     void* d_frames, uint64_t frame_stride, uint32_t* d_digests) {
+    const uint32_t mac = mac_len(algo);
+    // the segments' route, decided once for the call; a payload under 16 bytes holds only segments the
+    // join folds itself and never takes the plan (whose (0, 0) entries load base[0, 16))
+    const int route = (payload_size < 16u || indexed_direct(payload_size)) ? 0 : 1;
+    Carver cv;
+    const size_t o_crc = cv.take((size_t)std::max<uint64_t>(nseg, 1) * 4),
+                 o_off = cv.take(route == 1 ? (size_t)nseg * 8 : 0), o_len = cv.take(route == 1 ? (size_t)nseg * 4 : 0);
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // held across the nested plan (slot 0)
+    uint8_t* seg = nullptr;
+    hipError_t e = sc.get(2, cv.used, st, &seg);
+    if (e == hipSuccess) e = sc.flag(st);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("segment scratch: ") + hipGetErrorString(e));
+    uint32_t* segcrc = Carver::at<uint32_t>(seg, o_crc);
+    if (nseg) {
+        const uint64_t* offs = d_seg_offsets;
+        const uint32_t* lens = d_seg_lengths;
+        if (route == 1) {
+            uint64_t* poff = Carver::at<uint64_t>(seg, o_off);
+            uint32_t* plen = Carver::at<uint32_t>(seg, o_len);
+            const unsigned pblocks = (unsigned)std::min<uint64_t>((nseg + 255) / 256, 8u * (uint64_t)ds.cus);
+            hipLaunchKernelGGL(bkd::segments_for_plan_kernel, dim3(pblocks), dim3(256), 0, st, d_seg_offsets, d_seg_lengths,
+                               nseg, payload_size, poff, plen);
+            BKD_HIP(hipGetLastError());
+            offs = poff;
+            lens = plen;
+        }
+        const int rc = indexed_batch(ds, algo, (const uint8_t*)d_payload, payload_size, offs, lens, nseg, nullptr,
+                                     0xFFFFFFFFu, segcrc, st, nullptr, 0, route);
+        if (rc) return rc;
+    }
+    const uint32_t* x32tab = ds.tables[algo][lane_index(4)] + 1024;  // x^32 operator, 4 x 256
+    const uint64_t ntiles = (n + bkd::kSegJoinBlock - 1) / bkd::kSegJoinBlock;
+    const unsigned jblocks = (unsigned)std::min<uint64_t>(ntiles, 8u * (uint64_t)ds.cus);
+    hipLaunchKernelGGL(bkd::package_segments_join_kernel, dim3(jblocks), dim3(bkd::kSegJoinBlock), 0, st, x32tab,
+                       ds.xp8[algo], bkd::gf2::poly(algo), ledger_id, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields,
+                       (const uint8_t*)d_payload, payload_size, d_seg_offsets, d_seg_lengths, segcrc, d_seg_first, n, nseg,
+                       d_digests, sc.err);
+    BKD_HIP(hipGetLastError());
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (d_ledger_ids)
+        hipLaunchKernelGGL(bkd::package_frame_ledgers_kernel, dim3(blocks), dim3(256), 0, st, d_ledger_ids, d_entry_ids,
+                           d_lacs, d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
+    else
+        hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
+                           d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
 // Verify (bkd_digest_verify_batch and bkd_entrylog_verify): header CRCs -> payload CRCs seeded
 // with them through the indexed path (chunked plan for large ragged batches) -> compare. Batches
 // that take the plan route first run a gate over the frame lengths: when every frame is within
@@ -1315,10 +1384,76 @@ int resume_device(int algo, uint32_t current, const void* ptr, uint64_t len, hip
     return rc;
 }
 
-// The GPU route of bkd_digest_package_batch_host and bkd_digest_package_batch_ledgers_host
-// (h_ledger_ids: one ledger id per entry, staged as a fourth aux array; else ledger_id for all).
+// stage_entries as the `stage` argument of the staged routes below: entry i is the one buffer ptrs[i].
+auto entry_buffers(const void* const* ptrs, const uint32_t* lens) {
+    return [=](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) {
+        return stage_entries(hs, s, ptrs, lens, i0, cnt, bytes);
+    };
+}
+
+// Composite entries of a host-resident call (bkd_digest_package_batch_segments_host,
+// bkd_crc_batch_segments_host): entry i = segments first[i] .. first[i+1]-1, segment k its own host
+// buffer. at[k] = where segment k starts in the concatenation of the whole batch, so an entry's bytes
+// are at[first[i+1]] - at[first[i]] (entry_len[i], saturated at 2^32 - 1) and a staged run of entries
+// is one run of segments laid end to end: every staged entry is contiguous.
+struct HostSegments {
+    const void* const* ptrs;
+    const uint32_t* lens;
+    const uint64_t* first;
+    std::vector<uint64_t> at;
+    std::vector<uint32_t> entry_len;
+    HostSegments(const void* const* ptrs_, const uint32_t* lens_, uint64_t nseg, const uint64_t* first_, uint64_t n)
+        : ptrs(ptrs_), lens(lens_), first(first_), at(nseg + 1), entry_len(n) {
+        at[0] = 0;
+        for (uint64_t k = 0; k < nseg; ++k) at[k + 1] = at[k] + lens[k];
+        for (uint64_t i = 0; i < n; ++i)
+            entry_len[i] = (uint32_t)std::min<uint64_t>(at[first[i + 1]] - at[first[i]], 0xFFFFFFFFu);
+    }
+    // The `stage` argument of the staged routes: entries [i0, i0 + cnt) gathered into slot s's pinned
+    // buffer on the copy pool (split by bytes), then the bytes, where each entry landed and the
+    // entries' summed lengths copied H2D on the slot's stream.
+    int operator()(HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) const {
+        const uint64_t k0 = first[i0], k1 = first[i0 + cnt], b0 = at[k0];
+        for (uint64_t j = 0; j < cnt; ++j) hs.h_off[s][j] = at[first[i0 + j]] - b0;
+        uint8_t* dst = hs.h_pin[s];
+        const int parts = (int)std::min<uint64_t>((uint64_t)copy_threads(), std::max<uint64_t>(1, bytes / copy_part_bytes()));
+        const uint64_t per = (bytes + parts - 1) / parts;
+        bkd::host::Pool::get().run(parts, [&](int p) {
+            // segments whose first byte lies in [b0 + p*per, b0 + (p+1)*per)
+            const uint64_t lo = b0 + per * (uint64_t)p, hi = lo + per;
+            uint64_t k = (uint64_t)(std::lower_bound(at.data() + k0, at.data() + k1, lo) - at.data());
+            for (; k < k1 && at[k] < hi; ++k)
+                if (lens[k]) memcpy(dst + (at[k] - b0), ptrs[k], lens[k]);
+        });
+        if (bytes) BKD_HIP(hipMemcpyAsync(hs.d_buf[s], hs.h_pin[s], bytes, hipMemcpyHostToDevice, hs.st[s]));
+        BKD_HIP(hipMemcpyAsync(hs.d_off[s], hs.h_off[s], cnt * 8, hipMemcpyHostToDevice, hs.st[s]));
+        BKD_HIP(hipMemcpyAsync(hs.d_len[s], entry_len.data() + i0, cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+        return BKD_OK;
+    }
+};
+
+// Null-pointer checks and the CSR of the host-resident composite calls, before any work: seg_first
+// starts at 0, never decreases and ends at nseg (BKD_ERR_INVALID_ARG otherwise).
+int check_host_segments(const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths, uint64_t nseg,
+                        const uint64_t* h_seg_first, uint64_t n) {
+    if (!h_seg_first || (nseg && (!h_seg_ptrs || !h_seg_lengths))) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (h_seg_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "seg_first[0] is not 0");
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_seg_first[i + 1] < h_seg_first[i])
+            return fail(BKD_ERR_INVALID_ARG, "seg_first decreases at entry " + std::to_string(i));
+    if (h_seg_first[n] != nseg) return fail(BKD_ERR_INVALID_ARG, "seg_first[n] is not nseg");
+    for (uint64_t k = 0; k < nseg; ++k)
+        if (h_seg_lengths[k] && !h_seg_ptrs[k]) return fail(BKD_ERR_INVALID_ARG, "null segment " + std::to_string(k));
+    return BKD_OK;
+}
+
+// The GPU route of bkd_digest_package_batch_host, bkd_digest_package_batch_ledgers_host
+// (h_ledger_ids: one ledger id per entry, staged as a fourth aux array; else ledger_id for all) and
+// bkd_digest_package_batch_segments_host. stage(hs, s, i0, cnt, bytes) puts entries [i0, i0 + cnt)
+// back to back into slot s (entry_buffers, HostSegments); h_lengths[i] = entry i's bytes.
+template <class Stage>
 int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
-                        const int64_t* h_lacs, const int64_t* h_length_fields, const void* const* h_payloads,
+                        const int64_t* h_lacs, const int64_t* h_length_fields, const Stage& stage,
                         const uint32_t* h_lengths, uint64_t n, void* h_frames, uint64_t frame_stride,
                         uint32_t* h_digests) {
     StagedCall call(&HostStage::init_package);
@@ -1328,7 +1463,7 @@ int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids
     const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / frame_stride);
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
         const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        int r = stage(hs, s, i0, cnt, bytes);
         if (r) return r;
         int64_t* aux = reinterpret_cast<int64_t*>(hs.h_aux[s]);
         memcpy(aux, h_entry_ids + i0, cnt * 8);
@@ -1346,7 +1481,13 @@ int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids
         return BKD_OK;
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy((uint8_t*)h_frames + i0 * frame_stride, hs.h_frm[s], cnt * frame_stride);
+        // packed frames in one copy; with a wider stride only each frame's 32 + mac bytes (the bytes
+        // between frames are the caller's, and the device never wrote them)
+        const uint64_t hl = 32u + mac_len(algo);
+        uint8_t* dst = (uint8_t*)h_frames + i0 * frame_stride;
+        if (frame_stride == hl) memcpy(dst, hs.h_frm[s], cnt * hl);
+        else
+            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, hs.h_frm[s] + j * frame_stride, hl);
         memcpy(h_digests + i0, hs.h_res[s], cnt * 4);
         return BKD_OK;
     };
@@ -1874,8 +2015,8 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   h_digests);
         return BKD_OK;
     }
-    return package_host_staged(algo, ledger_id, nullptr, h_entry_ids, h_lacs, h_length_fields, h_payloads, h_lengths, n,
-                               h_frames, frame_stride, h_digests);
+    return package_host_staged(algo, ledger_id, nullptr, h_entry_ids, h_lacs, h_length_fields,
+                               entry_buffers(h_payloads, h_lengths), h_lengths, n, h_frames, frame_stride, h_digests);
 }
 
 int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
@@ -1983,8 +2124,8 @@ int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids,
                                           frame_stride, h_digests);
         return BKD_OK;
     }
-    return package_host_staged(algo, 0, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, h_payloads, h_lengths, n,
-                               h_frames, frame_stride, h_digests);
+    return package_host_staged(algo, 0, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                               entry_buffers(h_payloads, h_lengths), h_lengths, n, h_frames, frame_stride, h_digests);
 }
 
 int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check, uint32_t flags,
@@ -2108,6 +2249,105 @@ int bkd_crc_batch_segments(int algo, const void* d_base, uint64_t base_size, con
                        d_seg_first, n, nseg, d_seeds, seed_all, pw, bkd::gf2::poly(algo), d_out);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
+}
+
+int bkd_digest_package_batch_segments(int algo, int64_t ledger_id, const int64_t* d_ledger_ids,
+                                      const int64_t* d_entry_ids, const int64_t* d_lacs, const int64_t* d_length_fields,
+                                      const void* d_payload, uint64_t payload_size, const uint64_t* d_seg_offsets,
+                                      const uint32_t* d_seg_lengths, uint64_t nseg, const uint64_t* d_seg_first, uint64_t n,
+                                      void* d_frames, uint64_t frame_stride, uint32_t* d_digests, void* stream) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    const uint32_t mac = mac_len(algo);
+    if (n == 0) return BKD_OK;
+    if (!d_entry_ids || !d_lacs || !d_length_fields || !d_seg_first || !d_frames || !d_digests ||
+        (nseg && (!d_seg_offsets || !d_seg_lengths)))
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nseg && !d_payload && payload_size) return fail(BKD_ERR_INVALID_ARG, "null payload");
+    if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return package_segments(*call.ds, call.st, algo, ledger_id, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields,
+                            d_payload, payload_size, d_seg_offsets, d_seg_lengths, nseg, d_seg_first, n, d_frames,
+                            frame_stride, d_digests);
+}
+
+int bkd_digest_package_batch_segments_host(int algo, int64_t ledger_id, const int64_t* h_ledger_ids,
+                                           const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                           const int64_t* h_length_fields, const void* const* h_seg_ptrs,
+                                           const uint32_t* h_seg_lengths, uint64_t nseg, const uint64_t* h_seg_first,
+                                           uint64_t n, void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    const uint32_t mac = mac_len(algo);
+    if (n == 0) return BKD_OK;
+    if (!h_entry_ids || !h_lacs || !h_length_fields || !h_frames || !h_digests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (frame_stride < 32u + mac || frame_stride > 4096u)
+        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
+    int rc = check_host_segments(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
+    if (rc) return rc;
+    const HostSegments segs(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
+    const int route = framed_host_route(segs.entry_len.data(), n);
+    if (route < 0) return route;
+    if (route == 1) {
+        bkd::host::package_frames_segments(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                                           (const uint8_t* const*)h_seg_ptrs, h_seg_lengths, h_seg_first,
+                                           segs.entry_len.data(), n, (uint8_t*)h_frames, frame_stride, h_digests);
+        return BKD_OK;
+    }
+    return package_host_staged(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, segs,
+                               segs.entry_len.data(), n, h_frames, frame_stride, h_digests);
+}
+
+int bkd_crc_batch_segments_host(int algo, const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths, uint64_t nseg,
+                                const uint64_t* h_seg_first, uint64_t n, const uint32_t* h_seeds, uint32_t seed_all,
+                                uint32_t* h_out) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (n == 0) return BKD_OK;
+    if (!h_out) return fail(BKD_ERR_INVALID_ARG, "null out");
+    int rc = check_host_segments(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
+    if (rc) return rc;
+    const HostSegments segs(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
+    const int route = framed_host_route(segs.entry_len.data(), n);
+    if (route < 0) return route;
+    if (route == 1) {
+        bkd::host::crc_segments(algo, (const uint8_t* const*)h_seg_ptrs, h_seg_lengths, h_seg_first,
+                                segs.entry_len.data(), n, h_seeds, seed_all, h_out);
+        return BKD_OK;
+    }
+    StagedCall call;
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        const hipStream_t st = hs.st[s];
+        int r = segs(hs, s, i0, cnt, bytes);
+        if (r) return r;
+        if (h_seeds) {
+            memcpy(hs.h_seed[s], h_seeds + i0, cnt * 4);
+            BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, st));
+        }
+        r = indexed_batch(*call.ds, algo, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
+                          h_seeds ? hs.d_seed[s] : nullptr, seed_all, hs.d_res[s], st);
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy(h_out + i0, hs.h_res[s], cnt * 4);
+        return BKD_OK;
+    };
+    return host_segments(hs, segs.entry_len.data(), n, HostStage::kSegEntries, seg, drain);
+}
+
+int bkd_host_segments_range(uint64_t first_i, uint64_t first_i1, uint64_t i, uint64_t n, uint64_t nseg,
+                            uint64_t* k0, uint64_t* k1) {
+    const bkd::SegRange r = bkd::segments_range(first_i, first_i1, i, n, nseg);
+    if (k0) *k0 = r.k0;
+    if (k1) *k1 = r.k1;
+    return r.bad ? 1 : 0;
+}
+
+int bkd_host_segment_bytewise(uint64_t offset, uint32_t length, uint64_t payload_size) {
+    return bkd::segment_joined_bytewise(offset, length, payload_size) ? 1 : 0;
 }
 
 int bkd_entrylog_index(const void* h_log, uint64_t log_size, uint64_t start, uint64_t* h_offsets,

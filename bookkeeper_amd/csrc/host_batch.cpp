@@ -267,9 +267,12 @@ uint64_t verify_frames_by(int algo, Expected&& expected, const uint8_t* const* f
 // DigestManager.computeDigestAndPackageForSending (:117-181): header [ledgerId, entryId, LAC, length]
 // BE (:146-149), digest = update(update(0, header), payload) (:152-153), written after the header
 // (CRC32CDigestManager.java:44-46 writeInt; CRC32DigestManager.java:60-63 writeLong, zero-extended).
-template <class Ledger>
+// payload(i, reg, whole_pool) = the register after folding entry i's payload onto reg: one buffer
+// (one_buffer) or a composite's segments in order (Segments); lens[i] = the payload's bytes (the walk's
+// balance and its long-entry split).
+template <class Ledger, class Payload>
 void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, const int64_t* lacs,
-                       const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
+                       const int64_t* length_fields, Payload&& payload, const uint32_t* lens, uint64_t n,
                        uint8_t* frames, uint64_t stride, uint32_t* digests) {
     const uint32_t mac = mac_len(algo);
     walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
@@ -278,8 +281,7 @@ void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, cons
         put_be64(f + 8, (uint64_t)entry_ids[i]);
         put_be64(f + 16, (uint64_t)lacs[i]);
         put_be64(f + 24, (uint64_t)length_fields[i]);
-        uint32_t reg = crc_raw(algo, 0xFFFFFFFFu, f, 32);
-        if (lens[i]) reg = whole_pool ? fold(algo, reg, payloads[i], lens[i]) : crc_raw(algo, reg, payloads[i], lens[i]);
+        const uint32_t reg = payload(i, crc_raw(algo, 0xFFFFFFFFu, f, 32), whole_pool);
         const uint32_t d = ~reg;
         if (mac == 8u) put_be32(f + 32, 0u);
         put_be32(f + 32 + (mac - 4u), d);
@@ -343,18 +345,64 @@ void verify_frames_expected(int algo, const int64_t* ledger_ids, const int64_t* 
     }, frames, lens, n, status);
 }
 
+namespace {
+
+// Entry i's payload as one buffer of lens[i] bytes.
+auto one_buffer(int algo, const uint8_t* const* payloads, const uint32_t* lens) {
+    return [=](uint64_t i, uint32_t reg, bool whole_pool) {
+        if (!lens[i]) return reg;
+        return whole_pool ? fold(algo, reg, payloads[i], lens[i]) : crc_raw(algo, reg, payloads[i], lens[i]);
+    };
+}
+
+// Composite payloads: entry i = segments first[i] .. first[i+1]-1 in order, the register chained over
+// the non-empty ones as DigestManager.update chains it over ByteBufVisitor's leaves
+// (DigestManager.java:62-72, 380-392; ByteBufVisitor.java:100-103 skips empty buffers). Nothing is
+// copied together.
+struct Segments {
+    int algo;
+    const uint8_t* const* ptrs;
+    const uint32_t* lens;
+    const uint64_t* first;
+    uint32_t operator()(uint64_t i, uint32_t reg, bool whole_pool) const {
+        for (uint64_t k = first[i]; k < first[i + 1]; ++k)
+            if (lens[k]) reg = whole_pool ? fold(algo, reg, ptrs[k], lens[k]) : crc_raw(algo, reg, ptrs[k], lens[k]);
+        return reg;
+    }
+};
+
+}  // namespace
+
 void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                     const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
                     uint8_t* frames, uint64_t stride, uint32_t* digests) {
-    package_frames_by(algo, [&](uint64_t) { return ledger_id; }, entry_ids, lacs, length_fields, payloads, lens, n, frames,
-                      stride, digests);
+    package_frames_by(algo, [&](uint64_t) { return ledger_id; }, entry_ids, lacs, length_fields,
+                      one_buffer(algo, payloads, lens), lens, n, frames, stride, digests);
 }
 
 void package_frames_ledgers(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
                             const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
                             uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests) {
-    package_frames_by(algo, [&](uint64_t i) { return ledger_ids[i]; }, entry_ids, lacs, length_fields, payloads, lens, n,
-                      frames, stride, digests);
+    package_frames_by(algo, [&](uint64_t i) { return ledger_ids[i]; }, entry_ids, lacs, length_fields,
+                      one_buffer(algo, payloads, lens), lens, n, frames, stride, digests);
+}
+
+void package_frames_segments(int algo, int64_t ledger_id, const int64_t* ledger_ids, const int64_t* entry_ids,
+                             const int64_t* lacs, const int64_t* length_fields, const uint8_t* const* seg_ptrs,
+                             const uint32_t* seg_lens, const uint64_t* seg_first, const uint32_t* entry_lens,
+                             uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests) {
+    const Segments segs{algo, seg_ptrs, seg_lens, seg_first};
+    package_frames_by(algo, [&](uint64_t i) { return ledger_ids ? ledger_ids[i] : ledger_id; }, entry_ids, lacs,
+                      length_fields, segs, entry_lens, n, frames, stride, digests);
+}
+
+void crc_segments(int algo, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens, const uint64_t* seg_first,
+                  const uint32_t* entry_lens, uint64_t n, const uint32_t* seeds, uint32_t seed_all, uint32_t* out) {
+    const Segments segs{algo, seg_ptrs, seg_lens, seg_first};
+    walk(n, entry_lens, true, [&](uint64_t i, bool whole_pool, char&) {
+        out[i] = ~segs(i, ~(seeds ? seeds[i] : seed_all), whole_pool);
+        return 0;
+    });
 }
 
 // LedgerFragmentReplicator's second framing of an entry it has read and verified

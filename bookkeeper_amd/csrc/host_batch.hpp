@@ -81,6 +81,19 @@ void package_frames(int algo, int64_t ledger_id, const int64_t* entry_ids, const
 void package_frames_ledgers(int algo, const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
                             const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
                             uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests);
+// Composite payloads (bkd_digest_package_batch_segments_host, bkd_crc_batch_segments_host): entry i is
+// the concatenation of segments seg_first[i] .. seg_first[i+1]-1, segment k its own buffer seg_ptrs[k]
+// of seg_lens[k] bytes; the digest is chained over the non-empty ones (DigestManager.java:62-72,
+// 380-392), no bytes are copied together. seg_first is a valid CSR (the caller checked it).
+// entry_lens[i] = entry i's summed bytes, saturated at 2^32 - 1 (the caller has them from choosing the
+// route). ledger_ids[i] frames entry i when it is not null, else ledger_id.
+void package_frames_segments(int algo, int64_t ledger_id, const int64_t* ledger_ids, const int64_t* entry_ids,
+                             const int64_t* lacs, const int64_t* length_fields, const uint8_t* const* seg_ptrs,
+                             const uint32_t* seg_lens, const uint64_t* seg_first, const uint32_t* entry_lens,
+                             uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests);
+// out[i] = resume(seed_i, entry i's segments in order).
+void crc_segments(int algo, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens, const uint64_t* seg_first,
+                  const uint32_t* entry_lens, uint64_t n, const uint32_t* seeds, uint32_t seed_all, uint32_t* out);
 // Re-frames verified frames in place with new LACs (LedgerFragmentReplicator.java:436-442): status as
 // verify_frames (trusted: from the header alone, no payload byte read); a frame that is OK gets
 // new_lacs[i] at bytes 16..23 and the digest old ^ R(LAC difference) * x^(8 * payload length); the

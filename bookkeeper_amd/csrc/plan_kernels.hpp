@@ -701,6 +701,114 @@ __global__ void __launch_bounds__(1024, kPlanOcc) plan_combine_kernel(
     }
 }
 
+// ---- composite payloads framed (bkd_digest_package_batch_segments) ----
+// The segments an entry may touch, from its two CSR values: [k0, k1) with k0 <= k1 <= nseg whatever
+// the values are, and whether they break the CSR (a decrease, a value past nseg, a first value that is
+// not 0, a last value that is not nseg). Host and device: the CPU suite drives it with the malformed
+// arrays of the GPU tests before any of them runs (bkd_host_segments_range).
+struct SegRange {
+    uint64_t k0, k1;
+    bool bad;
+};
+__host__ __device__ inline SegRange segments_range(uint64_t first_i, uint64_t first_i1, uint64_t i, uint64_t n,
+                                                   uint64_t nseg) {
+    SegRange r;
+    r.bad = first_i1 < first_i || first_i1 > nseg || (i == 0u && first_i != 0u) || (i + 1u == n && first_i1 != nseg);
+    r.k1 = first_i1 < nseg ? first_i1 : nseg;
+    r.k0 = first_i < r.k1 ? first_i : r.k1;
+    return r;
+}
+
+// A segment the join kernel folds itself, byte by byte: in range and shorter than 16 bytes. The indexed
+// path's short-entry launch loads the whole 16-byte block at offset & ~15 of such an entry, an empty one
+// included (small_geo / small_load_idx, crc_kernels.hpp), which for a segment at the very end of the
+// payload lies past it; so on the plan route these segments reach the indexed path as (offset 0,
+// length 0) and their bytes, and only their bytes, are read here. (The range test cannot wrap.)
+__host__ __device__ inline bool segment_joined_bytewise(uint64_t off, uint32_t len, uint64_t size) {
+    return len < 16u && !(off > size || (uint64_t)len > size - off);
+}
+
+// The segments as the indexed path gets them on the plan route: those of segment_joined_bytewise as
+// (0, 0), every other one (out-of-range ones included: the indexed path skips and flags them) as it is.
+__global__ void __launch_bounds__(256) segments_for_plan_kernel(const uint64_t* __restrict__ seg_offsets,
+                                                                const uint32_t* __restrict__ seg_lengths,
+                                                                uint64_t nseg, uint64_t size,
+                                                                uint64_t* __restrict__ plan_offsets,
+                                                                uint32_t* __restrict__ plan_lengths) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nseg; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t o = seg_offsets[k];
+        const uint32_t l = seg_lengths[k];
+        const bool mine = segment_joined_bytewise(o, l, size);
+        plan_offsets[k] = mine ? 0u : o;
+        plan_lengths[k] = mine ? 0u : l;
+    }
+}
+
+// Entry i's digest from its header and its segments' zero-initialised registers (raw_k = ~segcrc[k],
+// the indexed path's output for seed ~0): the 32 header bytes [ledger id, entry id, LAC, length field]
+// built from the id arrays and folded from ~0 with the x^32 operator (package_header_kernel's fold,
+// update(0, header), DigestManager.java:146-153), then per non-empty segment
+// reg = reg * x^(8 len_k) ^ raw_k (DigestManager.update over ByteBufVisitor's leaves, :62-72, 380-392);
+// a segment of segment_joined_bytewise is folded onto reg from its own bytes instead (the byte table is
+// the x^32 operator's fourth quarter); digests[i] = ~reg. x^(8 len) is the product of the byte-power table's words XP[256 b + byte b of len]
+// (reframe_frame_kernel's table): one bitwise product per non-zero byte of the length, where
+// segments_combine_kernel's square-and-multiply takes one per set bit. One thread per entry, 256
+// entries a tile, grid stride over tiles so that both tables are staged in LDS once per block.
+// ledger_ids (may be null): one ledger id per entry in place of ledger_id.
+// (Defined ahead of segments_combine_kernel, which stays the last kernel of the code object: its
+// disassembly ends with the object's padding, and tools/kernel_disasm_diff.py compares that too.)
+constexpr int kSegJoinBlock = 256;
+__global__ void __launch_bounds__(kSegJoinBlock) package_segments_join_kernel(
+    const uint32_t* __restrict__ x32tab, const uint32_t* __restrict__ xp8tab, uint32_t poly, int64_t ledger_id,
+    const int64_t* __restrict__ ledger_ids, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
+    const int64_t* __restrict__ length_fields, const uint8_t* __restrict__ payload, uint64_t payload_size,
+    const uint64_t* __restrict__ seg_offsets, const uint32_t* __restrict__ seg_lengths,
+    const uint32_t* __restrict__ segcrc, const uint64_t* __restrict__ first, uint64_t n, uint64_t nseg,
+    uint32_t* __restrict__ digests, uint32_t* __restrict__ err) {
+    __shared__ uint32_t W[1024];   // x^32 operator, 4 x 256
+    __shared__ uint32_t XP[1024];  // XP[256 k + b] = x^(8 b 256^k)
+    for (int k = threadIdx.x; k < 1024; k += kSegJoinBlock) {
+        W[k] = x32tab[k];
+        XP[k] = xp8tab[k];
+    }
+    __syncthreads();
+    const uint64_t ntiles = (n + kSegJoinBlock - 1) / kSegJoinBlock;
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t i = tile * kSegJoinBlock + threadIdx.x;
+        if (i >= n) continue;
+        const SegRange sr = segments_range(first[i], first[i + 1], i, n, nseg);
+        if (sr.bad) atomicOr(err, 1u);
+        const uint64_t fld[4] = {(uint64_t)(ledger_ids ? ledger_ids[i] : ledger_id), (uint64_t)entry_ids[i],
+                                 (uint64_t)lacs[i], (uint64_t)length_fields[i]};
+        uint32_t reg = 0xFFFFFFFFu;  // update(0, header)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint64_t f = fld[k >> 1];
+            const uint32_t r = reg ^ __builtin_bswap32((k & 1) ? (uint32_t)f : (uint32_t)(f >> 32));
+            reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
+        }
+        for (uint64_t k = sr.k0; k < sr.k1; ++k) {
+            const uint32_t len = seg_lengths[k];
+            if (!len) continue;  // ByteBufVisitor skips empty buffers (ByteBufVisitor.java:100-103,146-149)
+            if (len < 16u) {
+                const uint64_t o = seg_offsets[k];
+                if (segment_joined_bytewise(o, len, payload_size)) {
+                    const uint8_t* q = payload + o;
+                    for (uint32_t j = 0; j < len; ++j) reg = W[768 + ((reg ^ q[j]) & 0xffu)] ^ (reg >> 8);
+                    continue;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t v = (len >> (8 * b)) & 0xffu;
+                if (v) reg = gf_mul_bits(XP[256 * b + v], reg, poly);
+            }
+            reg ^= ~segcrc[k];
+        }
+        digests[i] = ~reg;
+    }
+}
+
 // ---- composite entries (bkd_crc_batch_segments) ----
 // x^(8 * 2^b) mod P for b = 0..31: multiplying by x^(8*len) = one product per set bit of len.
 struct XPow8 {

@@ -242,6 +242,21 @@ class DigestManager:
                 _ck._stream_ptr(stream, framed)))
         return status, first_bad, digests
 
+    def package_batch_segments(self, entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths, seg_first,
+                               frame_stride=None, out_frames=None, stream=None, sync_check: bool = False):
+        """``package_batch`` for composite payloads (a CompositeByteBuf add, digested leaf by leaf:
+        DigestManager.java:62-72, 126-181): entry i's payload is the concatenation of segments
+        seg_first[i] .. seg_first[i+1]-1, segment k = payload[seg_offsets[k] : + seg_lengths[k]] (int64,
+        int32 and int64[n + 1] device tensors); empty segments are skipped and no bytes are copied
+        together. ``out_frames`` (uint8 device tensor): frame i is written at byte i * frame_stride of it
+        — it may lie inside `payload`, in bytes no segment touches; None: a new [n, frame_stride] tensor.
+        Returns (frames, digests int32[n]). An out-of-range segment or a malformed seg_first raises
+        BKD_ERR_BOUNDS from the stream's next ``stream_sync`` (here, when ``sync_check``).
+        Short and empty segments are legal anywhere, the payload's last byte and offset == size included:
+        the device reads no byte outside a segment shorter than 16 bytes."""
+        return _package_segments(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payload, seg_offsets,
+                                 seg_lengths, seg_first, frame_stride, out_frames, stream, sync_check)
+
     # ---- batch host path (new; entries in host memory, SURVEY §8f rows 1-2 / BASELINE config 5) ----
     def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
         """BatchedReadOp.complete over a ByteBufList (BatchedReadOp.java:164-190): `frames` is a
@@ -280,6 +295,16 @@ class DigestManager:
             vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
         del views
         return frames, digests
+
+    def package_batch_segments_host(self, entry_ids, lacs, length_fields, payloads, frame_stride=None):
+        """``package_batch_host`` for composite payloads: each payload is a bytes-like object, a sequence
+        of buffers, or a ``bytebuf.CompositeBuffer`` (its readable bytes, leaf by leaf as ``visit`` yields
+        them: nested composites, reader and writer indices honoured). The digest is chained over the
+        leaves as DigestManager.update chains it (DigestManager.java:62-72, 380-392); nothing is joined
+        in Python; empty leaves may be passed anywhere.
+        Returns (headers uint8[n, frame_stride] = [32 B header][digest], digests uint32[n])."""
+        return _package_segments_host(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payloads,
+                                      frame_stride)
 
     def reframe_batch_host(self, frames, first_entry_id: int, new_lacs, trusted: bool = False,
                            skip_entry_check: bool = False):
@@ -442,6 +467,98 @@ def package_batch_ledgers_host(digest_type, ledger_ids, entry_ids, lacs, length_
     return frames, digests
 
 
+# ---- composite payloads (a CompositeByteBuf add: DigestManager.java:62-72, 126-181, 380-392) ----
+
+def _package_segments(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths,
+                      seg_first, frame_stride, out_frames, stream, sync_check):
+    import torch
+    if algo is None:
+        raise NotImplementedError("DUMMY digests need no device work")
+    if seg_first.numel() < 1:
+        raise ValueError("seg_first holds n + 1 values")
+    n = seg_first.numel() - 1
+    nseg = seg_offsets.numel()
+    if seg_lengths.numel() != nseg:
+        raise ValueError("seg_offsets/seg_lengths size mismatch")
+    hl = METADATA_LENGTH + _mac_of(algo)
+    stride = frame_stride or hl
+    dev = payload.device
+    if out_frames is None:
+        out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    elif stride >= hl and n and out_frames.numel() * out_frames.element_size() < (n - 1) * stride + hl:
+        raise ValueError("out_frames is too small for n frames at this stride")
+    digests = torch.empty(n, dtype=torch.int32, device=dev)
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(lib().bkd_digest_package_batch_segments(
+            algo, ledger_id, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
+            _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n), _ck._dev_ptr(lacs, "lacs", i64, dev, n),
+            _ck._dev_ptr(length_fields, "length_fields", i64, dev, n), _ck._dev_ptr(payload, "payload"),
+            payload.numel() * payload.element_size(), _ck._dev_ptr(seg_offsets, "seg_offsets", i64, dev),
+            _ck._dev_ptr(seg_lengths, "seg_lengths", u32, dev), nseg, _ck._dev_ptr(seg_first, "seg_first", i64, dev), n,
+            _ck._dev_ptr(out_frames, "out_frames", torch.uint8, dev), stride, _ck._dev_ptr(digests, "digests"), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+    return out_frames, digests
+
+
+def package_batch_segments(digest_type, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths,
+                           seg_first, frame_stride=None, out_frames=None, stream=None, sync_check: bool = False):
+    """``DigestManager.package_batch_segments`` with ledger_ids[i] (int64[n]) framing entry i: an
+    aggregation queue's composite adds across ledgers in one launch sequence."""
+    if ledger_ids is None:
+        raise ValueError("ledger_ids holds one ledger id per entry")
+    return _package_segments(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets,
+                             seg_lengths, seg_first, frame_stride, out_frames, stream, sync_check)
+
+
+def _leaves(payload) -> list:
+    """The host buffers a payload is made of, in order: the readable leaves of a CompositeBuffer
+    (ByteBufVisitor's walk, bytebuf.CompositeBuffer.visit), one buffer for a bytes-like object, the
+    leaves of each element for a sequence of buffers."""
+    if isinstance(payload, CompositeBuffer):
+        return [_ck._host_view(leaf)[off:off + cnt]
+                for leaf, off, cnt in payload.visit(payload.reader_index, payload.readable_bytes())]
+    if isinstance(payload, (list, tuple)):
+        return [v for part in payload for v in _leaves(part)]
+    return [_ck._host_view(payload)]
+
+
+def _package_segments_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride):
+    if algo is None:
+        raise NotImplementedError("DUMMY digests need no device work")
+    leaves = [_leaves(p) for p in payloads]
+    n = len(leaves)
+    seg_first = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(l) for l in leaves], out=seg_first[1:])
+    views, ptrs, lens, first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
+    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
+    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
+    lac = np.ascontiguousarray(lacs, dtype=np.int64)
+    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
+    lids = None if ledger_ids is None else np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    if not (ids.size == lac.size == lf.size == n) or (lids is not None and lids.size != n):
+        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
+    frames = np.zeros((n, stride), dtype=np.uint8)
+    digests = np.zeros(n, dtype=np.uint32)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_package_batch_segments_host(
+        algo, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(first.ctypes.data), n,
+        vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
+    del views
+    return frames, digests
+
+
+def package_batch_segments_host(digest_type, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride=None):
+    """``DigestManager.package_batch_segments_host`` with ledger_ids[i] framing entry i."""
+    if ledger_ids is None:
+        raise ValueError("ledger_ids holds one ledger id per entry")
+    return _package_segments_host(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payloads,
+                                  frame_stride)
+
+
 class CRC32CDigestManager(DigestManager):
     """CRC32CDigestManager.java:27-62."""
     algo = CRC32C
@@ -485,3 +602,4 @@ class DummyDigestManager(DigestManager):
         raise NotImplementedError("DUMMY digests need no device work")
 
     verify_batch = package_batch_host = verify_batch_host = reframe_batch = reframe_batch_host = package_batch
+    package_batch_segments = package_batch_segments_host = package_batch

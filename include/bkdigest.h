@@ -223,7 +223,11 @@ BKD_API int bkd_digest_verify_batch(int algo, int64_t ledger_id, int64_t first_e
  * results back; CPU = DigestManager's per-entry arithmetic on the host threads. Synchronous.
  * verify: h_status[i] and *h_first_bad as bkd_digest_verify_batch (n if all verified).
  * package: writes frame i's [32 B header][digest] to h_frames + i*frame_stride
- * (32 + mac <= frame_stride <= 4096) and the digest value to h_digests[i]. */
+ * (32 + mac <= frame_stride <= 4096) and the digest value to h_digests[i]. Only those 32 + mac bytes of a
+ * frame's stride are written, on both routes. (Changed with the composite calls, for
+ * bkd_digest_package_batch_host and bkd_digest_package_batch_ledgers_host too: the GPU route used to copy
+ * whole strides back, so with frame_stride > 32 + mac it overwrote the bytes between frames with
+ * unspecified values; it now leaves them to the caller, as the CPU route always did.) */
 BKD_API int bkd_digest_verify_batch_host(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check,
                                          const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
                                          int32_t* h_status, uint64_t* h_first_bad);
@@ -277,6 +281,70 @@ BKD_API int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_led
                                                   const void* const* h_payloads, const uint32_t* h_lengths,
                                                   uint64_t n, void* h_frames, uint64_t frame_stride,
                                                   uint32_t* h_digests);
+
+/* ---- packaging composite payloads (a CompositeByteBuf add, digested leaf by leaf) -------------
+ * The add path hands DigestManager.computeDigestAndPackageForSending a composite payload — a Pulsar
+ * add is a CompositeByteBuf of a command/metadata buffer and the message payload — and the reference
+ * digests it leaf by leaf through ByteBufVisitor without copying the leaves together
+ * ($BK/proto/checksum/DigestManager.java:62-72, 126-181, 380-392; $BK/util/ByteBufVisitor.java:72-191).
+ * These calls take a batch of such adds whole, of one ledger or of many.
+ *
+ * Entry i's payload is the concatenation, in order, of segments seg_first[i] .. seg_first[i+1]-1
+ * (seg_first: n + 1 values from 0 to nseg, never decreasing). Empty segments are skipped, as the
+ * visitor skips empty leaves; an entry with no segments or only empty ones has an empty payload.
+ * Segments may be unaligned, in any order, overlapping, and shared between entries.
+ * Frame i = [32 B BE header: ledger id, entry_ids[i], lacs[i], length_fields[i]][digest] at
+ * frames + i*frame_stride (frame_stride >= 32 + mac; bytes of the stride past 32 + mac are not
+ * written), the ledger id being ledger_ids[i] or, when ledger_ids is NULL, ledger_id for all.
+ * digest = update(update(0, header), payload) (DigestManager.java:146-153, 172-178), written as
+ * bkd_digest_package_batch writes it, its value also to digests[i]. length_fields[i] is the caller's
+ * value as in bkd_digest_package_batch: it is not derived from the segments.
+ *
+ * Device-resident: segment k is d_payload + d_seg_offsets[k], d_seg_lengths[k] bytes. Asynchronous on
+ * `stream`, no host synchronisation; every payload byte is read once and none is copied (the segments
+ * take the indexed path; one kernel folds each header and joins its entry's segments in GF(2)). No
+ * byte of a frame may overlap a byte of a segment (the result is undefined otherwise); frames in front
+ * of their payloads inside d_payload are legal. A segment with offset + length > payload_size is not
+ * read and raises the stream's bounds flag (BKD_ERR_BOUNDS from the next bkd_stream_sync): that
+ * entry's digest is unspecified, its header is still written, every other entry is exact. A malformed
+ * d_seg_first (a decrease, a value past nseg, a first value that is not 0, a last that is not nseg) is
+ * clamped so that nothing outside the caller's arrays is read; it raises the same flag and leaves the
+ * outputs unspecified. n == 0 launches nothing; nseg == 0 with n > 0 is legal (all payloads empty).
+ * Short segments: the indexed path's short-entry launch loads whole 16-byte blocks for entries under
+ * 16 bytes, which at the very end of a buffer lie past it (bkd_crc_batch and bkd_crc_batch_segments have
+ * that property). This call does not: a segment shorter than 16 bytes, an empty one included, is never
+ * handed to that launch; the join kernel reads its own bytes and no others. An empty segment at
+ * offset == payload_size (an empty leaf at the writer index) and a short segment that ends on the
+ * payload's last byte are as legal as any. */
+BKD_API int bkd_digest_package_batch_segments(int algo, int64_t ledger_id, const int64_t* d_ledger_ids,
+                                              const int64_t* d_entry_ids, const int64_t* d_lacs,
+                                              const int64_t* d_length_fields, const void* d_payload,
+                                              uint64_t payload_size, const uint64_t* d_seg_offsets,
+                                              const uint32_t* d_seg_lengths, uint64_t nseg,
+                                              const uint64_t* d_seg_first, uint64_t n, void* d_frames,
+                                              uint64_t frame_stride, uint32_t* d_digests, void* stream);
+/* Host-resident: segment k is its own host buffer h_seg_ptrs[k] of h_seg_lengths[k] bytes — each
+ * CompositeByteBuf component's memoryAddress() and readableBytes(). Synchronous. The CSR is validated
+ * before any work (BKD_ERR_INVALID_ARG). Route as bkd_digest_package_batch_host
+ * (bkd_set_host_batch_route): CPU = the header's register, then the fold chained over the entry's
+ * non-empty segments, on the host threads, nothing copied together; GPU = an entry's segments laid end
+ * to end in pinned staging, then the device sequence of bkd_digest_package_batch. An entry whose
+ * segments sum to more than a staging segment (64 MiB) takes the CPU route, or returns
+ * BKD_ERR_INVALID_ARG when the GPU route is forced. 32 + mac <= frame_stride <= 4096. Short and empty
+ * segments are legal anywhere here too: the CPU route reads a segment's own bytes only, and the GPU
+ * route's staging buffer is allocated with room for the last 16-byte block. */
+BKD_API int bkd_digest_package_batch_segments_host(int algo, int64_t ledger_id, const int64_t* h_ledger_ids,
+                                                   const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                                   const int64_t* h_length_fields, const void* const* h_seg_ptrs,
+                                                   const uint32_t* h_seg_lengths, uint64_t nseg,
+                                                   const uint64_t* h_seg_first, uint64_t n, void* h_frames,
+                                                   uint64_t frame_stride, uint32_t* h_digests);
+/* bkd_crc_batch_segments for segments in host memory: h_out[i] = resume(seed_i, the concatenation of
+ * entry i's segments) (DigestManager.java:62-72, 380-392). Segments, CSR validation and routes as
+ * bkd_digest_package_batch_segments_host (GPU: the staged entries through the indexed path). */
+BKD_API int bkd_crc_batch_segments_host(int algo, const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths,
+                                        uint64_t nseg, const uint64_t* h_seg_first, uint64_t n,
+                                        const uint32_t* h_seeds, uint32_t seed_all, uint32_t* h_out);
 
 /* ---- re-framing verified entries with a new LAC (re-replication) -----------------------
  * LedgerFragmentReplicator frames every entry it has just read and verified a second time with the
@@ -356,6 +424,16 @@ BKD_API int64_t bkd_host_tables(int algo, int lanes, uint32_t* out, uint64_t out
 /* Host-only: GF(2) product a*b mod P in the reflected representation, and x^(8*nbytes) mod P. */
 BKD_API uint32_t bkd_host_gf_mul(int algo, uint32_t a, uint32_t b);
 BKD_API uint32_t bkd_host_xpow8n(int algo, uint64_t nbytes);
+/* Host-only: the clamp the device applies to entry i's two values of d_seg_first in
+ * bkd_digest_package_batch_segments (first_i = d_seg_first[i], first_i1 = d_seg_first[i + 1]):
+ * *k0 <= *k1 <= nseg is the range of segments the entry reads, whatever the values are; returns 1 when
+ * they break the CSR (the stream's bounds flag is raised), else 0. */
+BKD_API int bkd_host_segments_range(uint64_t first_i, uint64_t first_i1, uint64_t i, uint64_t n, uint64_t nseg,
+                                    uint64_t* k0, uint64_t* k1);
+/* Host-only: 1 when bkd_digest_package_batch_segments' join kernel folds this segment from its own
+ * bytes (in range and shorter than 16 bytes; it then reaches the indexed path as offset 0, length 0),
+ * else 0: the other bounds decision of that call, for the CPU suite. */
+BKD_API int bkd_host_segment_bytewise(uint64_t offset, uint32_t length, uint64_t payload_size);
 
 /* Tuning: lanes per entry group (0 = automatic, else 1/4/8/16/32/64); prefetch is fixed at build. */
 BKD_API int bkd_set_group_lanes(int lanes);
