@@ -919,7 +919,15 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
 // entry's header from the index arrays and folds header + payload in one pass, storing the digest
 // (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
 // d_ledger_ids (bkd_digest_package_batch_ledgers): one ledger id per entry instead of ledger_id; the
-// same routes through the *_ledgers_kernel forms, which read ledger_ids[i] beside entry_ids[i].
+// same routes and the same kernels, instantiated for the other id source.
+
+// Turns the ledger-id arguments into the package kernels' id source: f(bkd::LedgerPerEntry) when
+// d_ledger_ids is given, f(bkd::OneLedger) otherwise.
+template <class F>
+int with_ledger_ids(int64_t ledger_id, const int64_t* d_ledger_ids, F&& f) {
+    return d_ledger_ids ? f(bkd::LedgerPerEntry{d_ledger_ids}) : f(bkd::OneLedger{ledger_id});
+}
+
 int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_entry_ids,
                    const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
                    uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
@@ -938,47 +946,36 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     const uint64_t fr0 = (uint64_t)(uintptr_t)d_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
     const uint64_t pl0 = (uint64_t)(uintptr_t)d_payload, pl1 = pl0 + payload_size;
     const bool frames_apart = fr1 <= pl0 || pl1 <= fr0;
-    if (lanes >= 4 && frames_apart) {
-        rc = with_lanes<4>(lanes, [&](auto g) -> int {
-            constexpr int G = decltype(g)::value;
-            if (d_ledger_ids)
-                hipLaunchKernelGGL((bkd::crc_package_fused_ledgers_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
+    return with_ledger_ids(ledger_id, d_ledger_ids, [&](auto lid) -> int {
+        using Lid = decltype(lid);
+        if (lanes >= 4 && frames_apart) {
+            rc = with_lanes<4>(lanes, [&](auto g) -> int {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT, Lid>), dim3(group_blocks(ds, n, G)),
                                    dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths,
-                                   n, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields,
-                                   ds.tables[algo][lane_index(G)], d_digests, err, g_fold_sched.load());
-            else
-                hipLaunchKernelGGL((bkd::crc_package_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
-                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_payload, payload_size, d_offsets, d_lengths,
-                                   n, ledger_id, d_entry_ids, d_lacs, d_length_fields, ds.tables[algo][lane_index(G)],
+                                   n, lid, d_entry_ids, d_lacs, d_length_fields, ds.tables[algo][lane_index(G)],
                                    d_digests, err, g_fold_sched.load());
+                BKD_HIP(hipGetLastError());
+                return BKD_OK;
+            });
+            if (rc) return rc;
+            hipLaunchKernelGGL(bkd::package_frame_kernel<Lid>, dim3(blocks), dim3(256), 0, st, lid, d_entry_ids, d_lacs,
+                               d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
             BKD_HIP(hipGetLastError());
             return BKD_OK;
-        });
+        }
+        const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
+        hipLaunchKernelGGL(bkd::package_header_kernel<Lid>, dim3(hblocks), dim3(1024), 0, st, tab + 1024, lid,
+                           d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
+        BKD_HIP(hipGetLastError());
+        bkd::IndexedSrc src{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests};
+        rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
         if (rc) return rc;
-        if (d_ledger_ids)
-            hipLaunchKernelGGL(bkd::package_frame_ledgers_kernel, dim3(blocks), dim3(256), 0, st, d_ledger_ids,
-                               d_entry_ids, d_lacs, d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
-        else
-            hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
-                               d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
+        hipLaunchKernelGGL(bkd::package_digest_kernel, dim3(blocks), dim3(256), 0, st, d_digests, n,
+                           (uint8_t*)d_frames, frame_stride, mac);
         BKD_HIP(hipGetLastError());
         return BKD_OK;
-    }
-    const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
-    if (d_ledger_ids)
-        hipLaunchKernelGGL(bkd::package_header_ledgers_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, d_ledger_ids,
-                           d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
-    else
-        hipLaunchKernelGGL(bkd::package_header_kernel, dim3(hblocks), dim3(1024), 0, st, tab + 1024, ledger_id,
-                           d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
-    BKD_HIP(hipGetLastError());
-    bkd::IndexedSrc src{n, d_offsets, d_lengths, d_digests, 0u, payload_size, d_digests};
-    rc = dispatch_lanes(ds, lanes, algo, (const uint8_t*)d_payload, src, n, st, err);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bkd::package_digest_kernel, dim3(blocks), dim3(256), 0, st, d_digests, n,
-                       (uint8_t*)d_frames, frame_stride, mac);
-    BKD_HIP(hipGetLastError());
-    return BKD_OK;
+    });
 }
 
 // Package with composite payloads (bkd_digest_package_batch_segments): every segment's zero-initialised
@@ -1036,14 +1033,12 @@ int package_segments(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_i
                        d_digests, sc.err);
     BKD_HIP(hipGetLastError());
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (d_ledger_ids)
-        hipLaunchKernelGGL(bkd::package_frame_ledgers_kernel, dim3(blocks), dim3(256), 0, st, d_ledger_ids, d_entry_ids,
+    return with_ledger_ids(ledger_id, d_ledger_ids, [&](auto lid) -> int {
+        hipLaunchKernelGGL(bkd::package_frame_kernel<decltype(lid)>, dim3(blocks), dim3(256), 0, st, lid, d_entry_ids,
                            d_lacs, d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
-    else
-        hipLaunchKernelGGL(bkd::package_frame_kernel, dim3(blocks), dim3(256), 0, st, ledger_id, d_entry_ids, d_lacs,
-                           d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
-    BKD_HIP(hipGetLastError());
-    return BKD_OK;
+        BKD_HIP(hipGetLastError());
+        return BKD_OK;
+    });
 }
 
 // Verify (bkd_digest_verify_batch and bkd_entrylog_verify): header CRCs -> payload CRCs seeded
@@ -1069,8 +1064,8 @@ struct Requests {
 // rq (bkd_digest_verify_requests): per-request ledger ids, first entry ids, skip flags and verified
 // prefixes instead of ledger_id / first_entry_id / id_checks / d_first_bad. One more launch at the
 // head (request_expand_kernel: the CSR into per-entry expectations in the stream's scratch, the CSR
-// checked, the prefixes initialised); then the same gate and the same two routes, through the
-// *_requests_kernel forms.
+// checked, the prefixes initialised); then the same gate, the same two routes and the same kernels,
+// instantiated for bkd::RequestIds where one read's are for bkd::OneRead.
 int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, int64_t first_entry_id,
                   int id_checks, const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
                   const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad,
@@ -1139,49 +1134,42 @@ int verify_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, 
         const unsigned gblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, (uint64_t)ds.cus);
         hipLaunchKernelGGL(bkd::verify_gate_kernel, dim3(gblocks), dim3(1024), 0, st, d_lengths, n, d_first_bad, vflag,
                            vepoch);
-        // one kernel per lane count (crc_verify_fused_kernel); a forced one-lane geometry takes its
-        // narrowest group, 4
-        const int rc = with_lanes<4>(fused_lanes == 1 ? 4 : fused_lanes, [&](auto g) -> int {
-            constexpr int G = decltype(g)::value;
-            if (rq)
-                hipLaunchKernelGGL((bkd::crc_verify_fused_requests_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
-                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths,
-                                   n, mac, rids, ds.tables[algo][lane_index(G)], d_status, vflag, vepoch,
-                                   g_fold_sched.load());
-            else
-                hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT>), dim3(group_blocks(ds, n, G)),
-                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths,
-                                   n, mac, ledger_id, first_entry_id, id_checks, ds.tables[algo][lane_index(G)], d_status,
-                                   (unsigned long long*)d_first_bad, vflag, vepoch, g_fold_sched.load());
-            const hipError_t le = hipGetLastError();
-            return le == hipSuccess ? BKD_OK : fail(BKD_ERR_HIP, hipGetErrorString(le));
-        });
-        if (rc) return rc;
     }
-    const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
-    if (rq)
-        hipLaunchKernelGGL(bkd::verify_header_requests_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab,
-                           (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n, mac, rids, seeds, poff, plen,
+    // the launches that take the ids, written once for either source
+    auto run = [&](auto ids) -> int {
+        using Ids = decltype(ids);
+        if (fused) {
+            // one kernel per lane count (crc_verify_fused_kernel); a forced one-lane geometry takes its
+            // narrowest group, 4
+            const int rc = with_lanes<4>(fused_lanes == 1 ? 4 : fused_lanes, [&](auto g) -> int {
+                constexpr int G = decltype(g)::value;
+                hipLaunchKernelGGL((bkd::crc_verify_fused_kernel<G, kPF, kNT, Ids>), dim3(group_blocks(ds, n, G)),
+                                   dim3(bkd::kBlock), 0, st, (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths,
+                                   n, mac, ids, ds.tables[algo][lane_index(G)], d_status, vflag, vepoch,
+                                   g_fold_sched.load());
+                const hipError_t le = hipGetLastError();
+                return le == hipSuccess ? BKD_OK : fail(BKD_ERR_HIP, hipGetErrorString(le));
+            });
+            if (rc) return rc;
+        }
+        const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
+        hipLaunchKernelGGL(bkd::verify_header_kernel<Ids>, dim3(hblocks), dim3(1024), 0, st, x32tab,
+                           (const uint8_t*)d_framed, framed_size, d_offsets, d_lengths, n, mac, ids, seeds, poff, plen,
                            expect, pre, vflag, vepoch);
-    else
-        hipLaunchKernelGGL(bkd::verify_header_kernel, dim3(hblocks), dim3(1024), 0, st, x32tab, (const uint8_t*)d_framed,
-                           framed_size, d_offsets, d_lengths, n, mac, ledger_id, first_entry_id, id_checks, seeds, poff,
-                           plen, expect, pre, d_first_bad, vflag, vepoch);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
-    // payload CRCs land in d_status, then verify_finish turns them into status codes
-    int rc = indexed_batch(ds, algo, (const uint8_t*)d_framed, framed_size, poff, plen, n, seeds, 0,
-                           reinterpret_cast<uint32_t*>(d_status), st, vflag, vepoch, route);
-    if (rc) return rc;
-    if (rq)
-        hipLaunchKernelGGL(bkd::verify_finish_requests_kernel, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status,
-                           rids, vflag, vepoch);
-    else
-        hipLaunchKernelGGL(bkd::verify_finish_kernel, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status,
-                           (unsigned long long*)d_first_bad, vflag, vepoch);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
-    return BKD_OK;
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
+        // payload CRCs land in d_status, then verify_finish turns them into status codes
+        const int rc = indexed_batch(ds, algo, (const uint8_t*)d_framed, framed_size, poff, plen, n, seeds, 0,
+                                     reinterpret_cast<uint32_t*>(d_status), st, vflag, vepoch, route);
+        if (rc) return rc;
+        hipLaunchKernelGGL(bkd::verify_finish_kernel<Ids>, dim3(blocks), dim3(256), 0, st, expect, pre, n, d_status, ids,
+                           vflag, vepoch);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(BKD_ERR_HIP, hipGetErrorString(e));
+        return BKD_OK;
+    };
+    return rq ? run(rids)
+              : run(bkd::OneRead{ledger_id, first_entry_id, id_checks, (unsigned long long*)d_first_bad});
 }
 
 // Reframe (bkd_digest_reframe_batch): the verify sequence above (unless trusted), then one thread per

@@ -1512,13 +1512,68 @@ __device__ __forceinline__ uint32_t gf_mul_bits(uint32_t a, uint32_t b, uint32_t
 
 // ---- DigestManager framing helpers (one thread per entry; 32-byte headers) ----
 
+// Where an entry's ledger id comes from in the package kernels, passed as a kernel argument in the
+// scalar's place: one id for the launch (bkd_digest_package_batch) or one per entry
+// (bkd_digest_package_batch_ledgers). Each kernel below is one template on it.
+struct OneLedger {
+    int64_t id;
+    __device__ __forceinline__ int64_t operator()(uint64_t) const { return id; }
+};
+struct LedgerPerEntry {
+    const int64_t* __restrict__ ids;
+    __device__ __forceinline__ int64_t operator()(uint64_t i) const { return ids[i]; }
+};
+
+// The 32-byte header [ledgerId, entryId, LAC, length] (DigestManager.java:146-149) as the 8
+// little-endian dwords that hold its big-endian fields.
+__device__ __forceinline__ void header_dwords(int64_t ledger_id, int64_t entry_id, int64_t lac, int64_t length,
+                                              uint32_t* w) {
+    const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_id, (uint64_t)lac, (uint64_t)length};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
+        w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
+    }
+}
+
+// NW little-endian dwords folded onto reg with the x^32 operator W (4 x 256 words, staged in LDS):
+// 4 lookups per dword. A header's CRC register is fold_x32<8>(W, ~0, header dwords).
+template <int NW>
+__device__ __forceinline__ uint32_t fold_x32(const uint32_t* W, uint32_t reg, const uint32_t* w) {
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const uint32_t r = reg ^ w[k];
+        reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
+    }
+    return reg;
+}
+
+// A 32-byte header into a frame: 8 dwords when the frame is 4-byte aligned, else bytes.
+__device__ __forceinline__ void store_header(uint8_t* f, const uint32_t* w) {
+    if ((((uintptr_t)f) & 3u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
+    } else {
+        for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+    }
+}
+
+// The fused kernels' short payloads (under 16 bytes): serial bytes through the byte table at LDS byte
+// offset `tab` (ReflectedIntCrc.java:44-48 form).
+__device__ __forceinline__ uint32_t fold_bytes(const uint32_t* lds, uint32_t tab, uint32_t v, const uint8_t* q,
+                                               const uint8_t* end) {
+    for (; q < end; ++q) v = lds_word(lds, tab + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
+    return v;
+}
+
 // Package step 1: header [ledgerId, entryId, LAC, length] BE into the frame
 // (DigestManager.java:146-149 / :172-175) and its CRC (= the payload's seed) into seeds[i]. The
 // header is built as 8 little-endian dwords (byte-swapped BE fields), folded with the x^32 operator
 // (4 lookups per dword) and stored as dwords when the frame is 4-byte aligned.
 // Header kernels: grid stride (2 blocks of 1024 per CU), the x^32 tables staged once per block —
 // one 256-thread block per 256 entries staged them 4096 times per 1M entries (verify header 38 us).
-__global__ void __launch_bounds__(1024) package_header_kernel(const uint32_t* __restrict__ x32tab, int64_t ledger_id,
+template <class Lid>
+__global__ void __launch_bounds__(1024) package_header_kernel(const uint32_t* __restrict__ x32tab, Lid ledger_id,
                                                              const int64_t* __restrict__ entry_ids,
                                                              const int64_t* __restrict__ lacs,
                                                              const int64_t* __restrict__ length_fields, uint64_t n,
@@ -1528,28 +1583,11 @@ __global__ void __launch_bounds__(1024) package_header_kernel(const uint32_t* __
     for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_ids[i], (uint64_t)lacs[i],
-                             (uint64_t)length_fields[i]};
-    uint32_t w[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
-        w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
-    }
-    uint32_t reg = 0xFFFFFFFFu;  // update(0, header)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t r = reg ^ w[k];
-        reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
-    }
-    uint8_t* f = frames + i * frame_stride;
-    if ((((uintptr_t)f) & 3u) == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
-    } else {
-        for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
-    seeds[i] = ~reg;
+        uint32_t w[8];
+        header_dwords(ledger_id(i), entry_ids[i], lacs[i], length_fields[i], w);
+        const uint32_t reg = fold_x32<8>(W, 0xFFFFFFFFu, w);  // update(0, header)
+        store_header(frames + i * frame_stride, w);
+        seeds[i] = ~reg;
     }
 }
 
@@ -1566,7 +1604,8 @@ __global__ void __launch_bounds__(256) package_digest_kernel(const uint32_t* __r
 // The frames of the fused package route: each frame's 32-byte BE header (DigestManager.java:146-149)
 // and its digest at offset 32 (4-byte BE int, or 8-byte BE zero-extended long for CRC32) in one
 // pass after crc_package_fused_kernel, one frame per thread.
-__global__ void __launch_bounds__(256) package_frame_kernel(int64_t ledger_id, const int64_t* __restrict__ entry_ids,
+template <class Lid>
+__global__ void __launch_bounds__(256) package_frame_kernel(Lid ledger_id, const int64_t* __restrict__ entry_ids,
                                                             const int64_t* __restrict__ lacs,
                                                             const int64_t* __restrict__ length_fields,
                                                             const uint32_t* __restrict__ digests, uint64_t n,
@@ -1582,14 +1621,8 @@ __global__ void __launch_bounds__(256) package_frame_kernel(int64_t ledger_id, c
         const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x;
         const uint32_t cnt = (uint32_t)(n - i0 < (uint64_t)blockDim.x ? n - i0 : (uint64_t)blockDim.x);
         if (i < n) {
-            const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_ids[i], (uint64_t)lacs[i],
-                                     (uint64_t)length_fields[i]};
             uint32_t* w = fr + threadIdx.x * fw;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
-                w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
-            }
+            header_dwords(ledger_id(i), entry_ids[i], lacs[i], length_fields[i], w);
             if (mac == 8u) w[8] = 0u;
             w[fw - 1u] = __builtin_bswap32(digests[i]);
         }
@@ -1599,21 +1632,11 @@ __global__ void __launch_bounds__(256) package_frame_kernel(int64_t ledger_id, c
         return;
     }
     if (i >= n) return;
-    const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_ids[i], (uint64_t)lacs[i], (uint64_t)length_fields[i]};
     const uint32_t dg = digests[i];
     uint32_t w[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
-        w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
-    }
+    header_dwords(ledger_id(i), entry_ids[i], lacs[i], length_fields[i], w);
     uint8_t* f = frames + i * frame_stride;
-    if ((((uintptr_t)f) & 3u) == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
-    } else {
-        for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
+    store_header(f, w);
     put_frame_digest(f + 32, dg, mac);
 }
 
@@ -1715,13 +1738,8 @@ __global__ void __launch_bounds__(kReframeBlock) reframe_frame_kernel(
                 const uint64_t lac = (uint64_t)new_lacs[i];
                 const uint32_t n4 = __builtin_bswap32((uint32_t)(lac >> 32)), n5 = __builtin_bswap32((uint32_t)lac);
                 // R(D): the LAC difference's two dwords, then the length field's two zero dwords
-                uint32_t reg = 0u;
                 const uint32_t dw[4] = {w[4] ^ n4, w[5] ^ n5, 0u, 0u};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t r = reg ^ dw[k];
-                    reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
-                }
+                uint32_t reg = fold_x32<4>(W, 0u, dw);
                 // * x^(8 payload_len); equal LACs (reg == 0) need no product
                 const uint32_t plen = l - 32u - mac;
                 if (reg != 0u) {
@@ -1791,100 +1809,122 @@ __global__ void __launch_bounds__(kReframeBlock) reframe_frame_kernel(
 // first_bad = n before a TRUSTED reframe_frame_kernel, whose blocks lower it with atomicMin
 __global__ void reframe_first_bad_kernel(uint64_t* first_bad, uint64_t n) { *first_bad = n; }
 
+// ---- what the verify kernels check the header's ids against ----------------------------------
+// The id source `ids` is a kernel argument in the place of the scalars; each verify kernel is one
+// template on it. A kernel asks
+//   const auto x = ids.entry(i);  entry i's expectations (a source that loads them issues the loads here)
+//   x.id_status(hw, i)            0, 3 (ledger id mismatch, DigestManager.java:267-273) or 4 (entry id,
+//                                 :275-281) from the header's first four dwords as stored (big-endian)
+//   x.failed(i)                   entry i failed: lowers the verified-prefix word it belongs to
+//   ids.begin(n)                  verify_header_kernel's first thread, for a source whose prefix word
+//                                 no earlier launch has initialised
+
+// One read (bkd_digest_verify_batch, bkd_entrylog_verify): one ledger id, entry ids first_entry_id + i,
+// one verified-prefix word. id_checks: 0 ledger + entry ids, 1 ledger id only, 2 digest only
+// (entry-log scrub).
+struct OneRead {
+    int64_t ledger_id, first_entry_id;
+    int id_checks;
+    unsigned long long* first_bad;
+    __device__ __forceinline__ const OneRead& entry(uint64_t) const { return *this; }
+    __device__ __forceinline__ int32_t id_status(const uint32_t* hw, uint64_t i) const {
+        const int64_t lid = (int64_t)(((uint64_t)__builtin_bswap32(hw[0]) << 32) | __builtin_bswap32(hw[1]));
+        const int64_t eid = (int64_t)(((uint64_t)__builtin_bswap32(hw[2]) << 32) | __builtin_bswap32(hw[3]));
+        if (id_checks < 2 && lid != ledger_id) return 3;
+        if (id_checks == 0 && eid != first_entry_id + (int64_t)i) return 4;
+        return 0;
+    }
+    __device__ __forceinline__ void failed(uint64_t i) const { atomicMin(first_bad, (unsigned long long)i); }
+    __device__ __forceinline__ void begin(uint64_t n) const { *first_bad = n; }
+};
+
+// Read requests (bkd_digest_verify_requests): what request_expand_kernel writes per entry — the
+// expected ledger id and entry id and the entry's request (bit 31: the request skips the entry-id
+// check) — and where a failing entry lowers its request's verified prefix:
+// req_first_bad[r] = min(i - req_first[r]). The ids are compared as 32-bit halves, no 64-bit id is
+// rebuilt; the prefixes are request_expand_kernel's to initialise.
+constexpr uint32_t kReqSkipEntryId = 0x80000000u;
+
+struct RequestIds {
+    const int64_t* __restrict__ exp_lid;
+    const int64_t* __restrict__ exp_eid;
+    const uint32_t* __restrict__ req_of;
+    const uint64_t* __restrict__ req_first;
+    unsigned long long* req_first_bad;
+    struct Entry {
+        int64_t lid, eid;
+        uint32_t req;
+        const uint64_t* __restrict__ req_first;
+        unsigned long long* req_first_bad;
+        __device__ __forceinline__ int32_t id_status(const uint32_t* hw, uint64_t) const {
+            const uint32_t dl = (hw[0] ^ __builtin_bswap32((uint32_t)((uint64_t)lid >> 32))) |
+                                (hw[1] ^ __builtin_bswap32((uint32_t)lid));
+            const uint32_t de = (hw[2] ^ __builtin_bswap32((uint32_t)((uint64_t)eid >> 32))) |
+                                (hw[3] ^ __builtin_bswap32((uint32_t)eid));
+            return dl ? 3 : ((de && !(req & kReqSkipEntryId)) ? 4 : 0);
+        }
+        __device__ __forceinline__ void failed(uint64_t i) const {
+            const uint32_t r = req & ~kReqSkipEntryId;
+            atomicMin(req_first_bad + r, (unsigned long long)(i - req_first[r]));
+        }
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i) const {
+        return Entry{exp_lid[i], exp_eid[i], req_of[i], req_first, req_first_bad};
+    }
+    __device__ __forceinline__ void begin(uint64_t) const {}
+};
+
 // Verify step 1(one thread per framed entry [32 B header][mac][payload], DigestManager.java:226-283):
 // reads the header and the stored digest once — 16-byte loads when the frame is 16-byte aligned,
-// dword loads when 4-byte aligned, bytes otherwise — and writes everything step 3 needs, so that
-// step 3 touches no frame bytes:
+// dword loads when 4-byte aligned, bytes otherwise (load_frame_head) — and writes everything step 3
+// needs, so that step 3 touches no frame bytes:
 //   seeds[i]   CRC of the 32-byte header = the payload's seed (:236)
 //   pay_*[i]   the payload range [o + 32 + mac, o + l) step 2 folds (empty for a short entry)
 //   expect[i]  the stored digest (low 32 bits; CRC32DigestManager writes a zero-extended long)
 //   pre[i]     1 too short / out of range (:229-235); else bit 1 = high digest word non-zero,
 //              bits 2.. = the id check's code (3 ledger mismatch :267-273, 4 entry mismatch :275-281)
 // The header CRC folds 8 little-endian dwords with the x^32 operator (4 lookups per dword).
-__device__ __forceinline__ uint32_t be32_at(const uint32_t* w, int byte) {  // big-endian u32 at a 4-aligned byte
-    return __builtin_bswap32(w[byte >> 2]);
-}
-
-__global__ void __launch_bounds__(1024) verify_header_kernel(const uint32_t* __restrict__ x32tab,
-                                                            const uint8_t* __restrict__ framed, uint64_t size,
-                                                            const uint64_t* __restrict__ offsets,
-                                                            const uint32_t* __restrict__ lengths, uint64_t n,
-                                                            uint32_t mac, int64_t ledger_id, int64_t first_entry_id,
-                                                            int id_checks, uint32_t* __restrict__ seeds,
-                                                            uint64_t* __restrict__ pay_offsets,
-                                                            uint32_t* __restrict__ pay_lengths,
-                                                            uint32_t* __restrict__ expect, uint32_t* __restrict__ pre,
-                                                            uint64_t* __restrict__ first_bad,
-                                                            const uint32_t* __restrict__ vflag, uint32_t vepoch) {
+template <class Ids>
+__global__ void __launch_bounds__(1024) verify_header_kernel(
+    const uint32_t* __restrict__ x32tab, const uint8_t* __restrict__ framed, uint64_t size,
+    const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, Ids ids,
+    uint32_t* __restrict__ seeds, uint64_t* __restrict__ pay_offsets, uint32_t* __restrict__ pay_lengths,
+    uint32_t* __restrict__ expect, uint32_t* __restrict__ pre, const uint32_t* __restrict__ vflag, uint32_t vepoch) {
     if (vflag && *vflag != vepoch) return;  // near-uniform frames: crc_verify_fused_kernel does it all
     __shared__ uint32_t W[1024];
     for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
     __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x == 0) *first_bad = n;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ids.begin(n);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t o = offsets[i];
-    const uint32_t l = lengths[i];
-    if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
-        seeds[i] = 0u;
-        pay_offsets[i] = 0u;
-        pay_lengths[i] = 0u;
-        expect[i] = 0u;
-        pre[i] = 1u;
-        continue;
-    }
-    const uint8_t* f = framed + o;
-    uint32_t w[10];  // bytes [0, 40) of the frame as little-endian dwords (the first 32 + mac are used)
-    const int nw = (int)(32u + mac) / 4;
-    if ((((uintptr_t)f) & 15u) == 0 && l >= 48u) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(f + 16 * k);
-            if (4 * k < 10) w[4 * k] = v.x;
-            if (4 * k + 1 < 10) w[4 * k + 1] = v.y;
-            if (4 * k + 2 < 10) w[4 * k + 2] = v.z;
-            if (4 * k + 3 < 10) w[4 * k + 3] = v.w;
+        const uint64_t o = offsets[i];
+        const uint32_t l = lengths[i];
+        if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
+            seeds[i] = 0u;
+            pay_offsets[i] = 0u;
+            pay_lengths[i] = 0u;
+            expect[i] = 0u;
+            pre[i] = 1u;
+            continue;
         }
-    } else if ((((uintptr_t)f) & 3u) == 0) {
-        for (int k = 0; k < 10; ++k) w[k] = k < nw ? reinterpret_cast<const uint32_t*>(f)[k] : 0u;
-    } else {
-        for (int k = 0; k < 10; ++k) {
-            uint32_t v = 0u;
-            if (k < nw)
-                for (int b = 3; b >= 0; --b) v = (v << 8) | f[4 * k + b];
-            w[k] = v;
-        }
-    }
-    uint32_t reg = 0xFFFFFFFFu;  // update(0, header): resume from 0 = register ~0
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t r = reg ^ w[k];
-        reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
-    }
-    seeds[i] = ~reg;
-    pay_offsets[i] = o + 32u + mac;
-    pay_lengths[i] = l - 32u - mac;
-    const uint64_t lid = ((uint64_t)be32_at(w, 0) << 32) | be32_at(w, 4);
-    const uint64_t eid = ((uint64_t)be32_at(w, 8) << 32) | be32_at(w, 12);
-    uint32_t p = 0u;
-    if (mac == 8) {
-        if (w[8] != 0u) p |= 2u;
-        expect[i] = be32_at(w, 36);
-    } else {
-        expect[i] = be32_at(w, 32);
-    }
-    // id_checks: 0 ledger + entry ids, 1 ledger id only, 2 digest only (entry-log scrub)
-    if (id_checks < 2 && (int64_t)lid != ledger_id) p |= 3u << 2;
-    else if (id_checks == 0 && (int64_t)eid != first_entry_id + (int64_t)i) p |= 4u << 2;
-    pre[i] = p;
+        const auto x = ids.entry(i);
+        uint32_t w[10];  // bytes [0, 40) of the frame as little-endian dwords (the first 32 + mac are used)
+        load_frame_head(framed + o, l, mac, w);
+        seeds[i] = ~fold_x32<8>(W, 0xFFFFFFFFu, w);  // update(0, header): resume from 0 = register ~0
+        pay_offsets[i] = o + 32u + mac;
+        pay_lengths[i] = l - 32u - mac;
+        uint32_t p = (mac == 8u && w[8] != 0u) ? 2u : 0u;
+        expect[i] = __builtin_bswap32(mac == 8u ? w[9] : w[8]);
+        p |= (uint32_t)x.id_status(w, i) << 2;
+        pre[i] = p;
     }
 }
 
 // Verify step 3: per-entry status in DigestManager.verifyDigest's order (too short, digest, ledger id,
-// entry id) and the first failing index (BatchedReadOp.java:164-190 verified-prefix rule).
+// entry id) and the first failing index (BatchedReadOp.java:164-190 verified-prefix rule), per read.
+template <class Ids>
 __global__ void __launch_bounds__(256) verify_finish_kernel(const uint32_t* __restrict__ expect,
                                                             const uint32_t* __restrict__ pre, uint64_t n,
-                                                            int32_t* __restrict__ status,
-                                                            unsigned long long* __restrict__ first_bad,
+                                                            int32_t* __restrict__ status, Ids ids,
                                                             const uint32_t* __restrict__ vflag, uint32_t vepoch) {
     if (vflag && *vflag != vepoch) return;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1896,7 +1936,7 @@ __global__ void __launch_bounds__(256) verify_finish_kernel(const uint32_t* __re
     else if ((p & 2u) || computed != expect[i]) st = 2;
     else st = (int32_t)(p >> 2);
     status[i] = st;
-    if (st != 0) atomicMin(first_bad, (unsigned long long)i);
+    if (st != 0) ids.entry(i).failed(i);
 }
 
 // ---- fused verify for near-uniform frames ---------------------------------------------------
@@ -1925,11 +1965,12 @@ __global__ void __launch_bounds__(1024) verify_gate_kernel(const uint32_t* __res
 // finalized digest is stored here (digests[i], a wave's groups writing consecutive words); the
 // frames' header and digest bytes are written afterwards by package_frame_kernel, so no lone frame
 // store lands between this kernel's streaming payload reads. Out-of-range payloads: digest 0 and the
-// stream's bounds flag, as the indexed path reports them.
-template <int G, int PF, bool NT>
+// stream's bounds flag, as the indexed path reports them. A per-entry ledger id is one more per-group
+// load beside entry_ids[i], in flight with the payload's first loads.
+template <int G, int PF, bool NT, class Lid>
 __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
     const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
-    const uint32_t* __restrict__ lengths, uint64_t n, int64_t ledger_id, const int64_t* __restrict__ entry_ids,
+    const uint32_t* __restrict__ lengths, uint64_t n, Lid ledger_id, const int64_t* __restrict__ entry_ids,
     const int64_t* __restrict__ lacs, const int64_t* __restrict__ length_fields, const uint32_t* __restrict__ tables,
     uint32_t* __restrict__ digests, uint32_t* __restrict__ err, int sched) {
     using Gm = Geo<G>;
@@ -1944,7 +1985,9 @@ __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
     for (uint64_t i = gid; i < n; i += ngroups) {
         const uint64_t o = offsets[i];
         const uint32_t l = lengths[i];
-        const uint64_t f4[4] = {(uint64_t)ledger_id, (uint64_t)entry_ids[i], (uint64_t)lacs[i],
+        // (header_dwords() ahead of the branch compiles the single-ledger kernel to other machine code,
+        // 24 instructions fewer and not measured: the fields are swapped where they are folded)
+        const uint64_t f4[4] = {(uint64_t)ledger_id(i), (uint64_t)entry_ids[i], (uint64_t)lacs[i],
                                 (uint64_t)length_fields[i]};
         uint32_t d;
         if (o > size || (uint64_t)l > size - o) {
@@ -1963,10 +2006,8 @@ __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
                 return reg;
             };
             uint32_t v;
-            if (l < 16u) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
-                v = header_reg();
-                for (const uint8_t* q = base + o; q < base + o + l; ++q)
-                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
+            if (l < 16u) {  // short payload
+                v = fold_bytes(lds, Gm::kByteTabOff, header_reg(), base + o, base + o + l);
             } else {
                 const int64_t s = (int64_t)o, e = s + (int64_t)l;
                 const LateSeed<decltype(header_reg)> late{header_reg};
@@ -1980,12 +2021,16 @@ __global__ void __launch_bounds__(kBlock) crc_package_fused_kernel(
     held.finish(g, digests, gid, ngroups, n);
 }
 
-template <int G, int PF, bool NT>
+// The ids' expectations are asked for with offsets[i] / lengths[i], so a source that loads them has
+// its loads in flight with the header read. They are compared after the fold, where one read's scalars
+// are compared: RequestIds then holds its three loads across the fold (88-96 VGPRs against the 81-89
+// of comparing on arrival; one workgroup per CU either way, and not slower: DESIGN.md §5b). A failing
+// entry lowers its prefix word from lane 0 only.
+template <int G, int PF, bool NT, class Ids>
 __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
     const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
-    const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, int64_t ledger_id, int64_t first_entry_id,
-    int id_checks, const uint32_t* __restrict__ tables, int32_t* __restrict__ status,
-    unsigned long long* __restrict__ first_bad, const uint32_t* __restrict__ vflag, uint32_t vepoch, int sched) {
+    const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, Ids ids, const uint32_t* __restrict__ tables,
+    int32_t* __restrict__ status, const uint32_t* __restrict__ vflag, uint32_t vepoch, int sched) {
     using Gm = Geo<G>;
     if (*vflag == vepoch) return;  // some frame out of band: the header / plan / finish sequence runs
     __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
@@ -1999,6 +2044,7 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
     for (uint64_t i = gid; i < n; i += ngroups) {
         const uint64_t o = offsets[i];
         const uint32_t l = lengths[i];
+        const auto x = ids.entry(i);
         int32_t st;
         if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
             st = 1;  // VERIFY_TOO_SHORT (verify_header_kernel's rule for frames outside the buffer too)
@@ -2013,10 +2059,8 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
             for (int k = 0; k < 8; ++k) reg = mul_aux(lds, Gm::kX32Off, reg ^ hw[k]);
             const int64_t s = (int64_t)(o + 32u + mac), e = (int64_t)(o + l);
             uint32_t v;
-            if (e - s < 16) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
-                v = reg;
-                for (const uint8_t* q = base + s; q < base + e; ++q)
-                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
+            if (e - s < 16) {  // short payload
+                v = fold_bytes(lds, Gm::kByteTabOff, reg, base + s, base + e);
             } else {
                 v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, reg)
                               : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, reg);
@@ -2030,51 +2074,16 @@ __global__ void __launch_bounds__(kBlock) crc_verify_fused_kernel(
             } else {
                 expect = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 32));
             }
-            const int64_t lid = (int64_t)(((uint64_t)__builtin_bswap32(hw[0]) << 32) | __builtin_bswap32(hw[1]));
-            const int64_t eid = (int64_t)(((uint64_t)__builtin_bswap32(hw[2]) << 32) | __builtin_bswap32(hw[3]));
             // DigestManager.verifyDigest's order (DigestManager.java:226-283): digest, ledger id, entry id
-            if (hi != 0u || computed != expect) st = 2;
-            else if (id_checks < 2 && lid != ledger_id) st = 3;
-            else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) st = 4;
-            else st = 0;
+            st = (hi != 0u || computed != expect) ? 2 : x.id_status(hw, i);
         }
         held.put((uint32_t)st, g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
-        if (g == 0 && st != 0) atomicMin(first_bad, (unsigned long long)i);
+        if (g == 0 && st != 0) x.failed(i);
     }
     held.finish(g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
 }
 
-// ---- batches that span many ledgers (bkd_digest_verify_requests, bkd_digest_package_batch_ledgers) ----
-// The kernels above take one ledger id per launch. These forms take it per entry; they stand beside
-// the single-ledger kernels, whose machine code stays what it was (folding both onto one templated
-// body changed the single-ledger kernels' code: profiles/requests_kernel_disasm.txt),
-// and share their device functions (fold_range, HeldResults, mul_aux, put_frame_digest).
-
-// What request_expand_kernel writes per entry and the verify kernels read: the expected ledger id and
-// entry id and the entry's request (bit 31: the request skips the entry-id check), and where a
-// failing entry lowers its request's verified prefix: req_first_bad[r] = min(i - req_first[r]).
-constexpr uint32_t kReqSkipEntryId = 0x80000000u;
-
-struct RequestIds {
-    const int64_t* __restrict__ exp_lid;
-    const int64_t* __restrict__ exp_eid;
-    const uint32_t* __restrict__ req_of;
-    const uint64_t* __restrict__ req_first;
-    unsigned long long* req_first_bad;
-    // 0, 3 (ledger id mismatch, DigestManager.java:267-273) or 4 (entry id, :275-281) from the header's
-    // first four dwords as stored (big-endian): 32-bit halves, no 64-bit id is rebuilt
-    __device__ __forceinline__ static int32_t id_status(const uint32_t* hw, int64_t lid, int64_t eid, uint32_t req) {
-        const uint32_t dl = (hw[0] ^ __builtin_bswap32((uint32_t)((uint64_t)lid >> 32))) |
-                            (hw[1] ^ __builtin_bswap32((uint32_t)lid));
-        const uint32_t de = (hw[2] ^ __builtin_bswap32((uint32_t)((uint64_t)eid >> 32))) |
-                            (hw[3] ^ __builtin_bswap32((uint32_t)eid));
-        return dl ? 3 : ((de && !(req & kReqSkipEntryId)) ? 4 : 0);
-    }
-    __device__ __forceinline__ void failed(uint32_t req, uint64_t i) const {
-        const uint32_t r = req & ~kReqSkipEntryId;
-        atomicMin(req_first_bad + r, (unsigned long long)(i - req_first[r]));
-    }
-};
+// ---- read requests (bkd_digest_verify_requests) ----------------------------------------------
 
 // The CSR of bkd_digest_verify_requests into per-entry expectations. One thread per entry, a binary
 // search over req_first for the entry's request (the last r with req_first[r] <= i): the same code
@@ -2109,257 +2118,6 @@ __global__ void __launch_bounds__(256) request_expand_kernel(
         exp_eid[i] = (int64_t)((uint64_t)req_first_entry_ids[lo] + (i - req_first[lo]));
         req_of[i] = (uint32_t)lo | ((req_flags[lo] & 1u) ? kReqSkipEntryId : 0u);
     }
-}
-
-// crc_verify_fused_kernel's loop with per-entry expectations: their three loads leave with
-// offsets[i] / lengths[i], in flight with the header read; the ids are compared when the header
-// dwords arrive, so one status code is held across the payload fold, not two 64-bit ids; and a
-// failing entry lowers its request's prefix word (lane 0, on failure only).
-template <int G, int PF, bool NT>
-__global__ void __launch_bounds__(kBlock) crc_verify_fused_requests_kernel(
-    const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
-    const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, RequestIds ids,
-    const uint32_t* __restrict__ tables, int32_t* __restrict__ status, const uint32_t* __restrict__ vflag,
-    uint32_t vepoch, int sched) {
-    using Gm = Geo<G>;
-    if (*vflag == vepoch) return;  // some frame out of band: the header / plan / finish sequence runs
-    __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
-    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
-    const int lane = threadIdx.x & 63;
-    const int g = lane & (G - 1);
-    const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
-    const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
-    const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
-    HeldResults<G, kHoldStore> held;
-    for (uint64_t i = gid; i < n; i += ngroups) {
-        const uint64_t o = offsets[i];
-        const uint32_t l = lengths[i];
-        const int64_t xl = ids.exp_lid[i], xe = ids.exp_eid[i];
-        const uint32_t req = ids.req_of[i];
-        int32_t st;
-        if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
-            st = 1;  // VERIFY_TOO_SHORT (verify_header_kernel's rule for frames outside the buffer too)
-        } else {
-            const uint8_t* f = base + o;
-            const u32x4 h0 = ld16<false>(f), h1 = ld16<false>(f + 16);
-            const uint32_t hw[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            uint32_t reg = 0xFFFFFFFFu;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) reg = mul_aux(lds, Gm::kX32Off, reg ^ hw[k]);
-            const int32_t idst = RequestIds::id_status(hw, xl, xe, req);
-            const int64_t s = (int64_t)(o + 32u + mac), e = (int64_t)(o + l);
-            uint32_t v;
-            if (e - s < 16) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
-                v = reg;
-                for (const uint8_t* q = base + s; q < base + e; ++q)
-                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
-            } else {
-                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, reg)
-                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, reg);
-            }
-            const uint32_t computed = ~v;
-            // digest: 4-byte BE int (CRC32C) or 8-byte BE zero-extended long (CRC32) at offset 32
-            uint32_t expect, hi = 0u;
-            if (mac == 8u) {
-                hi = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 32));
-                expect = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 36));
-            } else {
-                expect = __builtin_bswap32(*reinterpret_cast<const uint32_t*>(f + 32));
-            }
-            // DigestManager.verifyDigest's order (DigestManager.java:226-283): digest, ledger id, entry id
-            st = (hi != 0u || computed != expect) ? 2 : idst;
-        }
-        held.put((uint32_t)st, g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
-        if (g == 0 && st != 0) ids.failed(req, i);
-    }
-    held.finish(g, reinterpret_cast<uint32_t*>(status), gid, ngroups, n);
-}
-
-// verify_header_kernel with the id checks read from the expanded arrays (and no first_bad word to
-// set: the per-request prefixes are request_expand_kernel's to initialise).
-__global__ void __launch_bounds__(1024) verify_header_requests_kernel(
-    const uint32_t* __restrict__ x32tab, const uint8_t* __restrict__ framed, uint64_t size,
-    const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n, uint32_t mac, RequestIds ids,
-    uint32_t* __restrict__ seeds, uint64_t* __restrict__ pay_offsets, uint32_t* __restrict__ pay_lengths,
-    uint32_t* __restrict__ expect, uint32_t* __restrict__ pre, const uint32_t* __restrict__ vflag, uint32_t vepoch) {
-    if (vflag && *vflag != vepoch) return;  // near-uniform frames: crc_verify_fused_requests_kernel does it all
-    __shared__ uint32_t W[1024];
-    for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t o = offsets[i];
-        const uint32_t l = lengths[i];
-        if (o > size || (uint64_t)l > size - o || l < 32u + mac) {
-            seeds[i] = 0u;
-            pay_offsets[i] = 0u;
-            pay_lengths[i] = 0u;
-            expect[i] = 0u;
-            pre[i] = 1u;
-            continue;
-        }
-        uint32_t w[10];
-        load_frame_head(framed + o, l, mac, w);
-        uint32_t reg = 0xFFFFFFFFu;  // update(0, header): resume from 0 = register ~0
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t r = reg ^ w[k];
-            reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
-        }
-        seeds[i] = ~reg;
-        pay_offsets[i] = o + 32u + mac;
-        pay_lengths[i] = l - 32u - mac;
-        uint32_t p = (mac == 8u && w[8] != 0u) ? 2u : 0u;
-        expect[i] = __builtin_bswap32(mac == 8u ? w[9] : w[8]);
-        p |= (uint32_t)RequestIds::id_status(w, ids.exp_lid[i], ids.exp_eid[i], ids.req_of[i]) << 2;
-        pre[i] = p;
-    }
-}
-
-// verify_finish_kernel with the verified prefix per request.
-__global__ void __launch_bounds__(256) verify_finish_requests_kernel(const uint32_t* __restrict__ expect,
-                                                                     const uint32_t* __restrict__ pre, uint64_t n,
-                                                                     int32_t* __restrict__ status, RequestIds ids,
-                                                                     const uint32_t* __restrict__ vflag,
-                                                                     uint32_t vepoch) {
-    if (vflag && *vflag != vepoch) return;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t computed = (uint32_t)status[i];
-    const uint32_t p = pre[i];
-    int32_t st;
-    if (p == 1u) st = 1;
-    else if ((p & 2u) || computed != expect[i]) st = 2;
-    else st = (int32_t)(p >> 2);
-    status[i] = st;
-    if (st != 0) ids.failed(ids.req_of[i], i);
-}
-
-// The 32-byte header [ledgerId, entryId, LAC, length] (DigestManager.java:146-149) as the 8
-// little-endian dwords that hold its big-endian fields.
-__device__ __forceinline__ void header_dwords(int64_t ledger_id, int64_t entry_id, int64_t lac, int64_t length,
-                                              uint32_t* w) {
-    const uint64_t fld[4] = {(uint64_t)ledger_id, (uint64_t)entry_id, (uint64_t)lac, (uint64_t)length};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        w[2 * k] = __builtin_bswap32((uint32_t)(fld[k] >> 32));
-        w[2 * k + 1] = __builtin_bswap32((uint32_t)fld[k]);
-    }
-}
-
-// package_header_kernel with ledger_ids[i] read beside entry_ids[i].
-__global__ void __launch_bounds__(1024) package_header_ledgers_kernel(
-    const uint32_t* __restrict__ x32tab, const int64_t* __restrict__ ledger_ids, const int64_t* __restrict__ entry_ids,
-    const int64_t* __restrict__ lacs, const int64_t* __restrict__ length_fields, uint64_t n, uint8_t* __restrict__ frames,
-    uint64_t frame_stride, uint32_t* __restrict__ seeds) {
-    __shared__ uint32_t W[1024];
-    for (int k = threadIdx.x; k < 1024; k += blockDim.x) W[k] = x32tab[k];
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t w[8];
-        header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
-        uint32_t reg = 0xFFFFFFFFu;  // update(0, header)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t r = reg ^ w[k];
-            reg = W[r & 0xffu] ^ W[256 + ((r >> 8) & 0xffu)] ^ W[512 + ((r >> 16) & 0xffu)] ^ W[768 + (r >> 24)];
-        }
-        uint8_t* f = frames + i * frame_stride;
-        if ((((uintptr_t)f) & 3u) == 0) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
-        } else {
-            for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-        }
-        seeds[i] = ~reg;
-    }
-}
-
-// package_frame_kernel with ledger_ids[i]: the packed LDS path and the per-thread path.
-__global__ void __launch_bounds__(256) package_frame_ledgers_kernel(
-    const int64_t* __restrict__ ledger_ids, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
-    const int64_t* __restrict__ length_fields, const uint32_t* __restrict__ digests, uint64_t n,
-    uint8_t* __restrict__ frames, uint64_t frame_stride, uint32_t mac) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (frame_stride == 32u + mac && (((uintptr_t)frames) & 3u) == 0) {
-        __shared__ uint32_t fr[256 * 10];
-        const uint32_t fw = (32u + mac) / 4u;  // dwords per frame
-        const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x;
-        const uint32_t cnt = (uint32_t)(n - i0 < (uint64_t)blockDim.x ? n - i0 : (uint64_t)blockDim.x);
-        if (i < n) {
-            uint32_t* w = fr + threadIdx.x * fw;
-            header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
-            if (mac == 8u) w[8] = 0u;
-            w[fw - 1u] = __builtin_bswap32(digests[i]);
-        }
-        __syncthreads();
-        uint32_t* dst = reinterpret_cast<uint32_t*>(frames + i0 * frame_stride);
-        for (uint32_t k = threadIdx.x; k < cnt * fw; k += blockDim.x) dst[k] = fr[k];
-        return;
-    }
-    if (i >= n) return;
-    const uint32_t dg = digests[i];
-    uint32_t w[8];
-    header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], w);
-    uint8_t* f = frames + i * frame_stride;
-    if ((((uintptr_t)f) & 3u) == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) reinterpret_cast<uint32_t*>(f)[k] = w[k];
-    } else {
-        for (int k = 0; k < 32; ++k) f[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
-    put_frame_digest(f + 32, dg, mac);
-}
-
-// crc_package_fused_kernel with ledger_ids[i]: one more per-group load beside entry_ids[i], in flight
-// with the payload's first loads (the header register is a late seed, as there).
-template <int G, int PF, bool NT>
-__global__ void __launch_bounds__(kBlock) crc_package_fused_ledgers_kernel(
-    const uint8_t* __restrict__ base, uint64_t size, const uint64_t* __restrict__ offsets,
-    const uint32_t* __restrict__ lengths, uint64_t n, const int64_t* __restrict__ ledger_ids,
-    const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs, const int64_t* __restrict__ length_fields,
-    const uint32_t* __restrict__ tables, uint32_t* __restrict__ digests, uint32_t* __restrict__ err, int sched) {
-    using Gm = Geo<G>;
-    __shared__ __attribute__((aligned(16))) uint32_t lds[Gm::kLdsWords];
-    const bool low_clock = stage_tables_low_clock<G>(lds, tables, sched);
-    const int lane = threadIdx.x & 63;
-    const int g = lane & (G - 1);
-    const uint32_t lanereg = ((uint32_t)(lane & 31) << 2) | (1u << 16);
-    const uint64_t ngroups = (uint64_t)gridDim.x * (kBlock / G);
-    const uint64_t gid = (uint64_t)blockIdx.x * (kBlock / G) + (uint64_t)(threadIdx.x / G);
-    HeldResults<G, kHoldStore> held;
-    for (uint64_t i = gid; i < n; i += ngroups) {
-        const uint64_t o = offsets[i];
-        const uint32_t l = lengths[i];
-        uint32_t hw[8];
-        header_dwords(ledger_ids[i], entry_ids[i], lacs[i], length_fields[i], hw);
-        uint32_t d;
-        if (o > size || (uint64_t)l > size - o) {
-            d = 0u;
-            if (g == 0 && err) atomicOr(err, 1u);
-        } else {
-            // update(0, header), evaluated by fold_range after the payload's first loads are issued
-            auto header_reg = [&]() {
-                uint32_t reg = 0xFFFFFFFFu;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) reg = mul_aux(lds, Gm::kX32Off, reg ^ hw[k]);
-                return reg;
-            };
-            uint32_t v;
-            if (l < 16u) {  // short payload: serial bytes (ReflectedIntCrc.java:44-48 form)
-                v = header_reg();
-                for (const uint8_t* q = base + o; q < base + o + l; ++q)
-                    v = lds_word(lds, Gm::kByteTabOff + (((v ^ *q) & 0xffu) << 2)) ^ (v >> 8);
-            } else {
-                const int64_t s = (int64_t)o, e = s + (int64_t)l;
-                const LateSeed<decltype(header_reg)> late{header_reg};
-                v = low_clock ? fold_range<G, PF, NT, false, false, true>(lds, lanereg, g, base, s, e, late)
-                              : fold_range<G, PF, NT, false, false, false>(lds, lanereg, g, base, s, e, late);
-            }
-            d = ~v;
-        }
-        held.put(d, g, digests, gid, ngroups, n);
-    }
-    held.finish(g, digests, gid, ngroups, n);
 }
 
 }  // namespace bkd

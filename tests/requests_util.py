@@ -152,7 +152,7 @@ def in_band(flens):
 @functools.lru_cache(maxsize=4)
 def fused_batch(algo, G):
     b = Batch(algo, fused_plens(G), short="cut")
-    assert in_band(b.flens)  # the gate passes: crc_verify_fused_requests_kernel verifies it
+    assert in_band(b.flens)  # the gate passes: crc_verify_fused_kernel<.., RequestIds> verifies it
     return b
 
 

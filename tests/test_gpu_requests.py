@@ -6,16 +6,19 @@ entry-id carry inside a request; two skip flags; every corruption kind placed by
 route of the verify sequence, with the geometry forced as test_gpu_framed_sweep.py forces it:
 
 * fused (plan mode 2, lengths within the gate's band: request_expand_kernel, then
-  crc_verify_fused_requests_kernel<G>) for G = 4 .. 64, both algorithms, both fold schedules;
+  crc_verify_fused_kernel<G, .., RequestIds>) for G = 4 .. 64, both algorithms, both fold schedules;
 * header / plan / finish (plan mode 2, payloads 0 .. 2600 bytes: out of band) and header / direct /
-  finish (plan mode 1): verify_header_requests_kernel, verify_finish_requests_kernel;
+  finish (plan mode 1): verify_header_kernel<RequestIds>, verify_finish_kernel<RequestIds>;
 * failures in different rounds of the fused kernel's grid stride than the prefix word they lower;
 * one request (bit for bit bkd_digest_verify_batch), one entry per request, 3 n requests, no entries;
 * a malformed CSR: BKD_ERR_BOUNDS from the stream's sync, nothing written outside the outputs, the
   stream usable afterwards; two streams at once, one of them with a malformed CSR;
-* package with per-entry ledger ids on the fused and the header-first route, package_frame_ledgers_kernel's
-  LDS and per-thread paths, equality with bkd_digest_package_batch for one ledger id, a round trip;
-* the host forms through the GPU with a request cut across staged segments.
+* package with per-entry ledger ids on the fused and the header-first route,
+  package_frame_kernel<LedgerPerEntry>'s LDS and per-thread paths, equality with
+  bkd_digest_package_batch for one ledger id, a round trip;
+* the host forms through the GPU with a request cut across staged segments;
+* the two id sources of each kernel against each other: one ledger id per call against the same id per
+  entry, one read against one request, on the same frames.
 
 Every status, prefix, frame byte and digest equals the oracle's.
 """
@@ -342,7 +345,7 @@ def test_package_batch_ledgers_routes(gpu, lanes, algo, schedule):
 
 @pytest.mark.parametrize("algo", ALGOS)
 def test_package_frame_ledgers_kernel_packed_and_misaligned(gpu, algo):
-    """package_frame_ledgers_kernel at the packed stride: the LDS path with n = 1, 255, 256, 257 and the
+    """package_frame_kernel<LedgerPerEntry> at the packed stride: the LDS path with n = 1, 255, 256, 257 and the
     per-thread path with the frame buffer 1, 2 and 3 bytes off a dword, between sentinel bytes."""
     import torch
     p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)
@@ -439,3 +442,64 @@ def test_host_forms_through_the_gpu_cut_a_request_across_segments(gpu):
         st, fb = dg.verify_requests_host(dt, views, first, ledgers, firsts)
     assert (st == want).all() and (st_c == want).all()
     assert fb.tolist() == fb_c.tolist() == [0, 3, 6, 1, 0]
+
+
+@pytest.mark.parametrize("algo", ALGOS)
+@pytest.mark.parametrize("lanes", fu.LANES)
+def test_id_sources_agree(gpu, lanes, algo):
+    """Every package and verify kernel is one template on where the ids come from; here both
+    instantiations get the same work. 257 frames of ledger L: package_batch and package_batch_ledgers
+    with L for every entry write the same bytes; verify_batch and verify_requests with one request give
+    the same statuses and the same verified prefix, on the intact frames and on frames with one
+    corrupted digest (2), one frame of another ledger (3) and one of another entry id (4), the last two
+    valid for the ids they carry. Frames of 48 .. 4096 bytes take header / direct / finish (plan mode 1)
+    and header / plan / finish (mode 2: out of the gate's band); frames within 64 bytes of the first,
+    mode 2, take the fused kernel. Equalities only."""
+    import torch
+    dt, n, hl = DTYPE[algo], 257, 32 + fu.MAC[algo]
+    L, first_id = 2**32 + 5, 2**32 - 100  # the entry ids carry into the high word
+    dm = dg.DigestManager.instantiate(L, b"", dt, False)
+    i64 = lambda a: _dev(torch, np.asarray(a, dtype=np.int64), gpu)
+    ids = first_id + np.arange(n, dtype=np.int64)
+    bad_digest, bad_ledger, bad_entry = 200, 131, 77
+    lids2, ids2 = np.full(n, L, dtype=np.int64), ids.copy()
+    lids2[bad_ledger] ^= 1 << 32
+    ids2[bad_entry] ^= 1 << 32
+    ragged = 48 + (np.arange(n, dtype=np.int64) * 1009) % (4096 - 48 + 1)
+    ragged[0], ragged[1] = 48, 4096
+    banded = 4096 - (np.arange(n, dtype=np.int64) * 7) % 65
+    for flens, modes in ((ragged, (1, 2)), (banded, (2,))):
+        assert rq.in_band(flens) == (flens is banded) and flens.min() >= 48 and flens.max() == 4096
+        plens = flens - hl
+        foffs, size = fu._place(flens, 7)
+        blob = oracle.fill_splitmix64(size, 3 + algo)
+        lenf = fu.LENGTH_FIELD_BASE + np.cumsum(plens)
+        d_blob, d_poff, d_plen = _dev(torch, blob, gpu), i64(foffs + hl), _dev(torch, plens.astype(np.int32), gpu)
+        d_off, d_len = i64(foffs), _dev(torch, flens.astype(np.int32), gpu)
+        rows = (foffs[:, None] + np.arange(hl)).reshape(-1)
+        one = (i64([0, n]), i64([L]), i64([first_id]))
+        for mode in modes:
+            with _forced(lanes, 1, mode):
+                for stride in (None, 64):
+                    f1, d1 = dm.package_batch(i64(ids), i64(ids - 1), i64(lenf), d_blob, d_poff, d_plen,
+                                              frame_stride=stride, sync_check=True)
+                    f2, d2 = dg.package_batch_ledgers(dt, i64(np.full(n, L)), i64(ids), i64(ids - 1), i64(lenf), d_blob,
+                                                      d_poff, d_plen, frame_stride=stride, sync_check=True)
+                    assert torch.equal(f1[:, :hl], f2[:, :hl]) and torch.equal(d1, d2), (mode, stride)
+                # frames valid for another ledger id and another entry id, from the per-entry form
+                f3, _ = dg.package_batch_ledgers(dt, i64(lids2), i64(ids2), i64(ids - 1), i64(lenf), d_blob, d_poff,
+                                                 d_plen, sync_check=True)
+                intact, broken = blob.copy(), blob.copy()
+                intact[rows] = f2.cpu().numpy()[:, :hl].reshape(-1)
+                broken[rows] = f3.cpu().numpy()[:, :hl].reshape(-1)
+                broken[foffs[bad_digest] + hl - 1] ^= 0x01
+                for what, framed, want in (("intact", intact, {}),
+                                           ("broken", broken, {bad_digest: 2, bad_ledger: 3, bad_entry: 4})):
+                    d_framed = _dev(torch, framed, gpu)
+                    st1, fb1 = dm.verify_batch(d_framed, d_off, d_len, first_id)
+                    st2, fb2 = dg.verify_requests(dt, d_framed, d_off, d_len, *one)
+                    ck.stream_sync(None)
+                    assert torch.equal(st1, st2), (what, mode)
+                    got = st1.cpu().numpy()
+                    assert {int(i): int(got[i]) for i in np.nonzero(got)[0]} == want, (what, mode)
+                    assert int(fb1.item()) == int(fb2[0].item()) == min(want, default=n), (what, mode)

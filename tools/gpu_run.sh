@@ -55,7 +55,9 @@ for step in "$@"; do
       else python3 tools/pmc_summary.py $O/pmc_fetch_uniform $O/pmc_write_uniform uniform4k $((1048576*4100)) > $O/pmc_u.json || exit 1; fi ;;
     pmc_verify|pmc_package)  # the framed routes on their own: --digest-op verify | package
       op=${step#pmc_}; cfg=${op}4k
-      # other kernels: the measured call's own launches (each bench also runs the other route once)
+      # other kernels: the measured call's own launches (each bench also runs the other route once);
+      # pmc_summary.py's short names, i.e. without template arguments: crc_verify_fused_kernel<8, 2, true,
+      # bkd::OneRead>, verify_header_kernel<bkd::OneRead>, package_frame_kernel<bkd::OneLedger> ... match as before
       if [ $op = verify ]; then mk=bkd::crc_verify_fused_kernel; ab=$((1048576*(4096+12+4)))
         ok=bkd::verify_gate_kernel,bkd::verify_header_kernel,bkd::plan_count_kernel,bkd::plan_scan_kernel,bkd::plan_emit_kernel,bkd::crc_plan_chunks_kernel,bkd::plan_combine_kernel,bkd::verify_finish_kernel
       else mk=bkd::crc_package_fused_kernel; ab=$((1048576*(4060+24+12+36+4))); ok=bkd::package_frame_kernel; fi
