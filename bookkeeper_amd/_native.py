@@ -29,6 +29,7 @@ VERIFY_ENTRY_MISMATCH = 4
 
 REFRAME_TRUSTED = 1  # BKD_REFRAME_TRUSTED
 REQUEST_SKIP_ENTRY_ID = 1  # BKD_REQUEST_SKIP_ENTRY_ID
+V2_SMALL_ENTRY_THRESHOLD = 16384  # BKD_V2_SMALL_ENTRY_THRESHOLD
 
 HEADER_PATH = os.path.join(ROOT, "include", "bkdigest.h")
 
@@ -85,6 +86,10 @@ PROTOTYPES = {
                                                  _vp, _u64, _vp, _vp]),
     "bkd_digest_package_batch_segments_host": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,
                                                       _u64, _vp]),
+    "bkd_digest_package_batch_v2": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32,
+                                           _u32, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_digest_package_batch_v2_host": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _u32,
+                                                _vp, _vp]),
     "bkd_crc_batch_segments_host": (_int, [_int, _vp, _vp, _u64, _vp, _u64, _vp, _u32, _vp]),
     "bkd_host_segment_bytewise": (_int, [_u64, _u32, _u64]),
     "bkd_host_segments_range": (_int, [_u64, _u64, _u64, _u64, _u64, _c.POINTER(_u64), _c.POINTER(_u64)]),

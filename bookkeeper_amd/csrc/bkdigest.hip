@@ -65,8 +65,10 @@ int lane_index(int lanes) {
 // DESIGN.md §5a), so the library keeps no device memory of its own in that pool.
 struct StreamScratch {
     std::recursive_mutex mu;
-    uint8_t* buf[3] = {};  // slot 0: plan scratch (launch_plan), 1: verify pipeline, 2: segment CRCs
-    size_t cap[3] = {};
+    static constexpr int kSlots = 4;
+    // slot 0: plan scratch (launch_plan), 1: verify pipeline, 2: segment CRCs, 3: package_v2's frames
+    uint8_t* buf[kSlots] = {};
+    size_t cap[kSlots] = {};
     // Sticky bounds-violation flag of the indexed batches enqueued on this stream (one per
     // stream, so a caller's out-of-range entry is reported to that caller's bkd_stream_sync
     // only); read and cleared in stream order. h_err: pinned landing word for the read.
@@ -920,6 +922,8 @@ int host_batch_pipelined(DeviceState& ds, HostStage& hs, int algo, const uint8_t
 // (crc_package_fused_kernel); package_frame_kernel then writes every frame's header and digest.
 // d_ledger_ids (bkd_digest_package_batch_ledgers): one ledger id per entry instead of ledger_id; the
 // same routes and the same kernels, instantiated for the other id source.
+// d_frames == nullptr (package_v2, which writes whole requests itself): only d_digests is wanted, and the
+// fused route ends after its first kernel. The header-first route needs frames to write its headers to.
 
 // Turns the ledger-id arguments into the package kernels' id source: f(bkd::LedgerPerEntry) when
 // d_ledger_ids is given, f(bkd::OneLedger) otherwise.
@@ -945,7 +949,7 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
     // front of their payloads keep the header-first route (0.821 vs 0.832 ms fused, profiles/r06r_*).
     const uint64_t fr0 = (uint64_t)(uintptr_t)d_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
     const uint64_t pl0 = (uint64_t)(uintptr_t)d_payload, pl1 = pl0 + payload_size;
-    const bool frames_apart = fr1 <= pl0 || pl1 <= fr0;
+    const bool frames_apart = !d_frames || fr1 <= pl0 || pl1 <= fr0;
     return with_ledger_ids(ledger_id, d_ledger_ids, [&](auto lid) -> int {
         using Lid = decltype(lid);
         if (lanes >= 4 && frames_apart) {
@@ -958,12 +962,13 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
                 BKD_HIP(hipGetLastError());
                 return BKD_OK;
             });
-            if (rc) return rc;
+            if (rc || !d_frames) return rc;
             hipLaunchKernelGGL(bkd::package_frame_kernel<Lid>, dim3(blocks), dim3(256), 0, st, lid, d_entry_ids, d_lacs,
                                d_length_fields, d_digests, n, (uint8_t*)d_frames, frame_stride, mac);
             BKD_HIP(hipGetLastError());
             return BKD_OK;
         }
+        if (!d_frames) return fail(BKD_ERR_INVALID_ARG, "the header-first package route needs a frame buffer");
         const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 1023) / 1024, 2u * (uint64_t)ds.cus);
         hipLaunchKernelGGL(bkd::package_header_kernel<Lid>, dim3(hblocks), dim3(1024), 0, st, tab + 1024, lid,
                            d_entry_ids, d_lacs, d_length_fields, n, (uint8_t*)d_frames, frame_stride, d_digests);
@@ -975,6 +980,65 @@ int package_framed(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id,
                            (uint8_t*)d_frames, frame_stride, mac);
         BKD_HIP(hipGetLastError());
         return BKD_OK;
+    });
+}
+
+// V2 add requests (bkd_digest_package_batch_v2; DigestManager.java:126-167): the digests exactly as
+// package_framed gets them (no frames wanted on its fused route; on the header-first route, which a
+// forced one-lane geometry takes, its frames go to the stream's scratch), then package_v2_head_kernel
+// (prefix, key, header and digest of every request) and package_v2_copy_kernel (the payloads under the
+// threshold, one lane group per entry). Two passes over the small payloads; no host sync. (A kernel
+// that copied each entry as its lane group folded it measured 14 % slower: DESIGN.md §3.)
+
+// Lanes per entry of package_v2_copy_kernel: about eight 16-byte blocks per lane (two turns of its loop
+// with four loads in flight), from 4 to 32 lanes. Measured at 4 KiB entries only: 32 lanes 2.47 ms per 1M
+// against 2.51 at 8 and 2.62 at 4, flat from 16 up. A forced lane width
+// (bkd_set_group_lanes) is the copy's too, its narrowest group for a one-lane geometry.
+int v2_copy_lanes(uint64_t mean_len) {
+    const int forced = g_forced_lanes.load();
+    if (forced) return std::max(forced, 4);
+    int g = 4;
+    while (g < 32 && (uint64_t)g * 2u * 128u <= mean_len) g *= 2;
+    return g;
+}
+
+int package_v2(DeviceState& ds, hipStream_t st, int algo, int64_t ledger_id, const int64_t* d_ledger_ids,
+               const int64_t* d_entry_ids, const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+               uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+               const uint8_t* d_keys, uint64_t key_stride, uint32_t packet_header, uint32_t small_threshold,
+               void* d_requests, uint64_t requests_size, const uint64_t* d_request_offsets, uint32_t* d_digests) {
+    const uint32_t mac = mac_len(algo);
+    const int lanes = auto_lanes(payload_size / n, n, ds.cus);
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // the digests and the request kernels as one sequence
+    uint32_t* err = nullptr;
+    int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    const bkd::V2Requests rq{(uint8_t*)d_requests, requests_size, d_request_offsets, mac, small_threshold};
+    uint8_t* frames = nullptr;
+    if (lanes < 4) {
+        const hipError_t e = sc.get(3, (size_t)n * (32u + mac), st, &frames);
+        if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("package_v2 scratch: ") + hipGetErrorString(e));
+    }
+    rc = package_framed(ds, st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
+                        d_offsets, d_lengths, n, frames, 32u + mac, d_digests, d_ledger_ids);
+    if (rc) return rc;
+    const unsigned hblocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 8u * (uint64_t)ds.cus);
+    return with_ledger_ids(ledger_id, d_ledger_ids, [&](auto lid) -> int {
+        using Lid = decltype(lid);
+        hipLaunchKernelGGL(bkd::package_v2_head_kernel<Lid>, dim3(hblocks), dim3(256), 0, st, lid, d_entry_ids, d_lacs,
+                           d_length_fields, d_lengths, d_digests, n, d_keys, key_stride, packet_header, rq, err);
+        BKD_HIP(hipGetLastError());
+        if (small_threshold == 0u) return BKD_OK;
+        return with_lanes<4>(v2_copy_lanes(payload_size / n), [&](auto g) -> int {
+            constexpr int G = decltype(g)::value;
+            const uint64_t per_block = 256 / G;
+            const unsigned cblocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, 8u * (uint64_t)ds.cus);
+            hipLaunchKernelGGL(bkd::package_v2_copy_kernel<G>, dim3(cblocks), dim3(256), 0, st, (const uint8_t*)d_payload,
+                               payload_size, d_offsets, d_lengths, n, rq);
+            BKD_HIP(hipGetLastError());
+            return BKD_OK;
+        });
     });
 }
 
@@ -1439,11 +1503,13 @@ int check_host_segments(const void* const* h_seg_ptrs, const uint32_t* h_seg_len
 // (h_ledger_ids: one ledger id per entry, staged as a fourth aux array; else ledger_id for all) and
 // bkd_digest_package_batch_segments_host. stage(hs, s, i0, cnt, bytes) puts entries [i0, i0 + cnt)
 // back to back into slot s (entry_buffers, HostSegments); h_lengths[i] = entry i's bytes.
-template <class Stage>
+// out(frames, digests, i0, cnt) takes a finished segment's results from the pinned landing buffers:
+// frame j of entries [i0, i0 + cnt) at frames + j*frame_stride (host_frames: into the caller's frame
+// array; bkd_digest_package_batch_v2_host: into its requests).
+template <class Stage, class Out>
 int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
                         const int64_t* h_lacs, const int64_t* h_length_fields, const Stage& stage,
-                        const uint32_t* h_lengths, uint64_t n, void* h_frames, uint64_t frame_stride,
-                        uint32_t* h_digests) {
+                        const uint32_t* h_lengths, uint64_t n, uint64_t frame_stride, const Out& out) {
     StagedCall call(&HostStage::init_package);
     if (call.rc) return call.rc;
     HostStage& hs = **call.lease;
@@ -1469,17 +1535,24 @@ int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids
         return BKD_OK;
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        out(hs.h_frm[s], hs.h_res[s], i0, cnt);
+        return BKD_OK;
+    };
+    return host_segments(hs, h_lengths, n, max_entries, seg, drain);
+}
+
+// package_host_staged's `out` for the calls that return a frame array and the digests.
+auto host_frames(int algo, void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
+    return [=](const uint8_t* frm, const uint32_t* res, uint64_t i0, uint64_t cnt) {
         // packed frames in one copy; with a wider stride only each frame's 32 + mac bytes (the bytes
         // between frames are the caller's, and the device never wrote them)
         const uint64_t hl = 32u + mac_len(algo);
         uint8_t* dst = (uint8_t*)h_frames + i0 * frame_stride;
-        if (frame_stride == hl) memcpy(dst, hs.h_frm[s], cnt * hl);
+        if (frame_stride == hl) memcpy(dst, frm, cnt * hl);
         else
-            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, hs.h_frm[s] + j * frame_stride, hl);
-        memcpy(h_digests + i0, hs.h_res[s], cnt * 4);
-        return BKD_OK;
+            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, frm + j * frame_stride, hl);
+        memcpy(h_digests + i0, res, cnt * 4);
     };
-    return host_segments(hs, h_lengths, n, max_entries, seg, drain);
 }
 
 }  // namespace
@@ -1643,7 +1716,7 @@ int bkd_stream_release(void* stream) {
             if (*sc->h_err) status = fail(BKD_ERR_BOUNDS, kBoundsMsg);
         }
         BKD_HIP(hipStreamSynchronize(call.st));  // the stream's own work is done with them
-        for (int k = 0; k < 3; ++k)
+        for (int k = 0; k < StreamScratch::kSlots; ++k)
             if (sc->buf[k]) BKD_HIP(hipFree(sc->buf[k]));
         for (uint32_t* w : {sc->err, sc->run, sc->uni, sc->vflag})
             if (w) BKD_HIP(hipFree(w));
@@ -2004,7 +2077,67 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
         return BKD_OK;
     }
     return package_host_staged(algo, ledger_id, nullptr, h_entry_ids, h_lacs, h_length_fields,
-                               entry_buffers(h_payloads, h_lengths), h_lengths, n, h_frames, frame_stride, h_digests);
+                               entry_buffers(h_payloads, h_lengths), h_lengths, n, frame_stride,
+                               host_frames(algo, h_frames, frame_stride, h_digests));
+}
+
+int bkd_digest_package_batch_v2(int algo, int64_t ledger_id, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                const uint8_t* d_master_keys, uint64_t key_stride, uint32_t flags,
+                                uint32_t small_threshold, void* d_requests, uint64_t requests_size,
+                                const uint64_t* d_request_offsets, uint32_t* d_digests, void* stream) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
+    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (n == 0) return BKD_OK;
+    if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_master_keys || !d_requests ||
+        !d_request_offsets || !d_digests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return package_v2(*call.ds, call.st, algo, ledger_id, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields, d_payload,
+                      payload_size, d_offsets, d_lengths, n, d_master_keys, key_stride,
+                      bkd::host::v2_packet_header(flags), small_threshold, d_requests, requests_size,
+                      d_request_offsets, d_digests);
+}
+
+int bkd_digest_package_batch_v2_host(int algo, int64_t ledger_id, const int64_t* h_ledger_ids,
+                                     const int64_t* h_entry_ids, const int64_t* h_lacs, const int64_t* h_length_fields,
+                                     const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
+                                     const uint8_t* h_master_keys, uint64_t key_stride, uint32_t flags,
+                                     uint32_t small_threshold, void* const* h_requests, uint32_t* h_digests) {
+    if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
+    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
+    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (n == 0) return BKD_OK;
+    if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_master_keys || !h_requests ||
+        !h_digests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+        if (!h_requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
+    }
+    const int route = framed_host_route(h_lengths, n);
+    if (route < 0) return route;
+    const bkd::host::V2Head head{h_master_keys, key_stride, bkd::host::v2_packet_header(flags), small_threshold};
+    const uint8_t* const* payloads = (const uint8_t* const*)h_payloads;
+    uint8_t* const* requests = (uint8_t* const*)h_requests;
+    if (route == 1) {
+        bkd::host::package_requests_v2(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, payloads,
+                                       h_lengths, n, head, requests, h_digests);
+        return BKD_OK;
+    }
+    // GPU: staged and digested as bkd_digest_package_batch_host; each finished segment's packed frames
+    // go into the requests behind the prefix the host writes, the small payloads from their sources
+    const uint64_t hl = 32u + mac_len(algo);
+    return package_host_staged(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                               entry_buffers(h_payloads, h_lengths), h_lengths, n, hl,
+                               [&](const uint8_t* frm, const uint32_t* res, uint64_t i0, uint64_t cnt) {
+                                   bkd::host::finish_requests_v2(algo, frm, payloads + i0, h_lengths + i0, cnt, head, i0,
+                                                                 requests + i0, copy_threads());
+                                   memcpy(h_digests + i0, res, cnt * 4);
+                               });
 }
 
 int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
@@ -2113,7 +2246,8 @@ int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids,
         return BKD_OK;
     }
     return package_host_staged(algo, 0, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
-                               entry_buffers(h_payloads, h_lengths), h_lengths, n, h_frames, frame_stride, h_digests);
+                               entry_buffers(h_payloads, h_lengths), h_lengths, n, frame_stride,
+                               host_frames(algo, h_frames, frame_stride, h_digests));
 }
 
 int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check, uint32_t flags,
@@ -2283,7 +2417,8 @@ int bkd_digest_package_batch_segments_host(int algo, int64_t ledger_id, const in
         return BKD_OK;
     }
     return package_host_staged(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, segs,
-                               segs.entry_len.data(), n, h_frames, frame_stride, h_digests);
+                               segs.entry_len.data(), n, frame_stride,
+                               host_frames(algo, h_frames, frame_stride, h_digests));
 }
 
 int bkd_crc_batch_segments_host(int algo, const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths, uint64_t nseg,

@@ -269,14 +269,14 @@ uint64_t verify_frames_by(int algo, Expected&& expected, const uint8_t* const* f
 // (CRC32CDigestManager.java:44-46 writeInt; CRC32DigestManager.java:60-63 writeLong, zero-extended).
 // payload(i, reg, whole_pool) = the register after folding entry i's payload onto reg: one buffer
 // (one_buffer) or a composite's segments in order (Segments); lens[i] = the payload's bytes (the walk's
-// balance and its long-entry split).
-template <class Ledger, class Payload>
-void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, const int64_t* lacs,
+// balance and its long-entry split). frame_at(i) = where entry i's [32 B header][digest] goes.
+template <class Ledger, class Payload, class FrameAt>
+void package_frames_at(int algo, Ledger&& ledger, const int64_t* entry_ids, const int64_t* lacs,
                        const int64_t* length_fields, Payload&& payload, const uint32_t* lens, uint64_t n,
-                       uint8_t* frames, uint64_t stride, uint32_t* digests) {
+                       FrameAt&& frame_at, uint32_t* digests) {
     const uint32_t mac = mac_len(algo);
     walk(n, lens, true, [&](uint64_t i, bool whole_pool, char&) {
-        uint8_t* f = frames + i * stride;
+        uint8_t* f = frame_at(i);
         put_be64(f, (uint64_t)ledger(i));
         put_be64(f + 8, (uint64_t)entry_ids[i]);
         put_be64(f + 16, (uint64_t)lacs[i]);
@@ -288,6 +288,23 @@ void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, cons
         digests[i] = d;
         return 0;
     });
+}
+
+template <class Ledger, class Payload>
+void package_frames_by(int algo, Ledger&& ledger, const int64_t* entry_ids, const int64_t* lacs,
+                       const int64_t* length_fields, Payload&& payload, const uint32_t* lens, uint64_t n,
+                       uint8_t* frames, uint64_t stride, uint32_t* digests) {
+    package_frames_at(algo, ledger, entry_ids, lacs, length_fields, payload, lens, n,
+                      [=](uint64_t i) { return frames + i * stride; }, digests);
+}
+
+// The 28 bytes in front of a V2 request's header (DigestManager.java:138-142): headersSize + payloadSize
+// (Java int arithmetic: 4 + 20 + 32 + mac + len), the packet header, the master key.
+constexpr uint32_t kV2Prefix = 28;
+inline void put_v2_prefix(uint8_t* r, uint32_t mac, uint32_t len, const V2Head& head, uint64_t i) {
+    put_be32(r, 56u + mac + len);
+    put_be32(r + 4, head.packet_header);
+    memcpy(r + 8, head.keys + i * head.key_stride, 20);
 }
 
 }  // namespace
@@ -394,6 +411,46 @@ void package_frames_segments(int algo, int64_t ledger_id, const int64_t* ledger_
     const Segments segs{algo, seg_ptrs, seg_lens, seg_first};
     package_frames_by(algo, [&](uint64_t i) { return ledger_ids ? ledger_ids[i] : ledger_id; }, entry_ids, lacs,
                       length_fields, segs, entry_lens, n, frames, stride, digests);
+}
+
+void package_requests_v2(int algo, int64_t ledger_id, const int64_t* ledger_ids, const int64_t* entry_ids,
+                         const int64_t* lacs, const int64_t* length_fields, const uint8_t* const* payloads,
+                         const uint32_t* lens, uint64_t n, const V2Head& head, uint8_t* const* requests,
+                         uint32_t* digests) {
+    const uint32_t mac = mac_len(algo);
+    const auto fold_one = one_buffer(algo, payloads, lens);
+    package_frames_at(
+        algo, [&](uint64_t i) { return ledger_ids ? ledger_ids[i] : ledger_id; }, entry_ids, lacs, length_fields,
+        [&](uint64_t i, uint32_t reg, bool whole_pool) {
+            uint8_t* r = requests[i];
+            put_v2_prefix(r, mac, lens[i], head, i);
+            reg = fold_one(i, reg, whole_pool);
+            // copied while the fold has it in the cache (isSmallEntry, :128, :160-163)
+            if (lens[i] && lens[i] < head.small) memcpy(r + kV2Prefix + 32u + mac, payloads[i], lens[i]);
+            return reg;
+        },
+        lens, n, [=](uint64_t i) { return requests[i] + kV2Prefix; }, digests);
+}
+
+void finish_requests_v2(int algo, const uint8_t* frames, const uint8_t* const* payloads, const uint32_t* lens,
+                        uint64_t n, const V2Head& head, uint64_t first, uint8_t* const* requests, int threads) {
+    const uint32_t mac = mac_len(algo), hl = 32u + mac;
+    // split by bytes written, as the staging gather is: the head counts for every entry
+    std::vector<uint64_t> at(n + 1);
+    at[0] = 0;
+    for (uint64_t i = 0; i < n; ++i) at[i + 1] = at[i] + kV2Prefix + hl + (lens[i] < head.small ? lens[i] : 0u);
+    const int parts = (int)std::min<uint64_t>((uint64_t)std::max(1, threads), std::max<uint64_t>(1, at[n] >> 20));
+    const uint64_t per = (at[n] + parts - 1) / parts;
+    Pool::get().run(parts, [&](int p) {
+        const uint64_t lo = per * (uint64_t)p, hi = lo + per;
+        uint64_t i = (uint64_t)(std::lower_bound(at.begin(), at.begin() + n, lo) - at.begin());
+        for (; i < n && at[i] < hi; ++i) {
+            uint8_t* r = requests[i];
+            put_v2_prefix(r, mac, lens[i], head, first + i);
+            memcpy(r + kV2Prefix, frames + i * hl, hl);
+            if (lens[i] && lens[i] < head.small) memcpy(r + kV2Prefix + hl, payloads[i], lens[i]);
+        }
+    });
 }
 
 void crc_segments(int algo, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens, const uint64_t* seg_first,

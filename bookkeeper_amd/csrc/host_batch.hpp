@@ -91,6 +91,29 @@ void package_frames_segments(int algo, int64_t ledger_id, const int64_t* ledger_
                              const int64_t* lacs, const int64_t* length_fields, const uint8_t* const* seg_ptrs,
                              const uint32_t* seg_lens, const uint64_t* seg_first, const uint32_t* entry_lens,
                              uint64_t n, uint8_t* frames, uint64_t stride, uint32_t* digests);
+// V2 add requests (bkd_digest_package_batch_v2_host; DigestManager.computeDigestAndPackageForSendingV2,
+// DigestManager.java:126-167): request i = [int32 BE 56 + mac + lens[i]][int32 BE packet header]
+// [20 B master key][32 B header][digest], then the payload when lens[i] < small (:128, :160-163).
+// PacketHeader.toInt(CURRENT_PROTOCOL_VERSION = 2, ADDENTRY = 1, flags) ($BK/proto/BookieProtocol.java:47,
+// 75-83, 114).
+inline uint32_t v2_packet_header(uint32_t flags) { return (2u << 24) | (1u << 16) | (flags & 0xFFFFu); }
+struct V2Head {
+    const uint8_t* keys;   // entry i's 20-byte key at keys + i*key_stride (key_stride 0: one key for all)
+    uint64_t key_stride;
+    uint32_t packet_header;
+    uint32_t small;        // payloads shorter than this are copied into the request
+};
+// The CPU route: package_frames' arithmetic per entry with the frame at requests[i] + 28, the prefix in
+// front of it, and the payload copied in right after it was folded (ledger_ids as package_frames_segments).
+void package_requests_v2(int algo, int64_t ledger_id, const int64_t* ledger_ids, const int64_t* entry_ids,
+                         const int64_t* lacs, const int64_t* length_fields, const uint8_t* const* payloads,
+                         const uint32_t* lens, uint64_t n, const V2Head& head, uint8_t* const* requests,
+                         uint32_t* digests);
+// The GPU route's last step for entries [first, first + n) (the arrays start at entry `first`, the keys
+// at entry 0): the prefix, frame i of the packed [32 B header][digest] frames the device returned, and
+// the small payloads from their sources, on at most `threads` pool threads.
+void finish_requests_v2(int algo, const uint8_t* frames, const uint8_t* const* payloads, const uint32_t* lens,
+                        uint64_t n, const V2Head& head, uint64_t first, uint8_t* const* requests, int threads);
 // out[i] = resume(seed_i, entry i's segments in order).
 void crc_segments(int algo, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens, const uint64_t* seg_first,
                   const uint32_t* entry_lens, uint64_t n, const uint32_t* seeds, uint32_t seed_all, uint32_t* out);

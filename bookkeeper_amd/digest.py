@@ -257,7 +257,36 @@ class DigestManager:
         return _package_segments(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payload, seg_offsets,
                                  seg_lengths, seg_first, frame_stride, out_frames, stream, sync_check)
 
+    def package_batch_v2(self, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key, *,
+                         key_stride=None, flags: int = FLAG_NONE, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD,
+                         requests=None, request_offsets=None, align: int = 1, stream=None, sync_check: bool = False):
+        """The V2 add requests of n device-resident entries, whole (computeDigestAndPackageForSendingV2,
+        DigestManager.java:126-167): request i = [int32 56 + mac + length][int32 packet header][20 B master
+        key][32 B header][digest], and the payload copied in behind it when it is shorter than
+        ``small_threshold`` (SMALL_ENTRY_SIZE_THRESHOLD; a larger entry's payload stays where it is, the
+        second buffer of the reference's ByteBufList). ``master_key``: 20 bytes for all entries, or a
+        uint8 device tensor of per-entry keys ``key_stride`` (default: its row length) bytes apart.
+        ``request_offsets`` (int64 device tensor) with ``requests`` (uint8 device tensor) place request i
+        at requests[request_offsets[i]:], any alignment, not overlapping; without them the requests are
+        laid out in order, each on a multiple of ``align`` bytes (1: packed; sizing the new tensor is
+        this path's one host sync — pass ``requests`` as well to avoid it). Bytes between requests are
+        not written. Returns (requests, request_offsets, digests int32[n]). An out-of-range payload
+        (digest 0, nothing copied) or a request outside ``requests`` (not written) raises BKD_ERR_BOUNDS
+        from the stream's next ``stream_sync`` (here, when ``sync_check``)."""
+        return _package_v2(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payload, offsets, lengths,
+                           master_key, key_stride, flags, small_threshold, requests, request_offsets, align, stream,
+                           sync_check)
+
     # ---- batch host path (new; entries in host memory, SURVEY §8f rows 1-2 / BASELINE config 5) ----
+    def package_batch_v2_host(self, entry_ids, lacs, length_fields, payloads, master_key, *, key_stride=None,
+                              flags: int = FLAG_NONE, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD):
+        """``package_batch_v2`` for payloads in host memory (a sequence of buffers): returns (requests, a
+        list of uint8 arrays, request i whole — the bytes computeDigestAndPackageForSending returns with
+        useV2Protocol for a small entry, its first 60 + mac bytes for a large one; digests uint32[n]).
+        ``master_key``: 20 bytes for all, or n rows of uint8 keys."""
+        return _package_v2_host(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payloads, master_key,
+                                key_stride, flags, small_threshold)
+
     def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
         """BatchedReadOp.complete over a ByteBufList (BatchedReadOp.java:164-190): `frames` is a
         sequence of host buffers, each one framed entry. Returns (status int32[n], first_bad) with
@@ -559,6 +588,135 @@ def package_batch_segments_host(digest_type, ledger_ids, entry_ids, lacs, length
                                   frame_stride)
 
 
+# ---- V2 add requests, packaged whole (DigestManager.java:126-167) ----
+
+V2_PREFIX_LENGTH = 4 + 4 + MASTER_KEY_LENGTH  # the two ints and the master key in front of the header
+
+
+def request_sizes_v2(algo: int, lengths, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD):
+    """Bytes of each V2 request buffer (bufferSize, DigestManager.java:135): 60 + mac, and the payload
+    when it is shorter than `small_threshold`. `lengths`: a numpy array or a torch tensor."""
+    head = V2_PREFIX_LENGTH + METADATA_LENGTH + _mac_of(algo)
+    if isinstance(lengths, np.ndarray):
+        l = lengths.astype(np.int64)
+        return head + np.where(l < small_threshold, l, 0)
+    import torch
+    l = lengths.to(torch.int64) & 0xFFFFFFFF  # (an int32 tensor holds the u32 lengths' bit patterns)
+    return head + torch.where(l < small_threshold, l, torch.zeros_like(l))
+
+
+def request_offsets_v2(sizes, align: int = 1):
+    """Requests laid out in order, each starting on a multiple of `align` bytes (1: packed):
+    (offsets int64[n], total bytes as a 0-d array / tensor)."""
+    if align < 1:
+        raise ValueError("align must be at least 1")
+    slots = (sizes + (align - 1)) // align * align
+    ends = slots.cumsum(0)
+    return ends - slots, (ends[-1] if len(ends) else ends.sum())
+
+
+def _master_keys(master_key, n: int, key_stride, to_device=None):
+    """(keys, key_stride): one 20-byte key for all (bytes-like: stride 0), or per-entry keys, a uint8
+    array / tensor of n rows of `key_stride` >= 20 bytes (default: its row length)."""
+    if isinstance(master_key, (bytes, bytearray, memoryview)):
+        key = bytes(master_key)
+        if len(key) < MASTER_KEY_LENGTH:
+            raise ValueError("a master key holds 20 bytes")
+        if key_stride not in (None, 0):
+            raise ValueError("one key for all entries has key_stride 0")
+        keys = np.frombuffer(key[:MASTER_KEY_LENGTH], dtype=np.uint8)
+        return (to_device(keys) if to_device else keys), 0
+    rows = master_key.shape[-1] if master_key.ndim > 1 else MASTER_KEY_LENGTH
+    stride = rows if key_stride is None else int(key_stride)
+    size = master_key.numel() if to_device else master_key.size
+    if stride < MASTER_KEY_LENGTH or (n and size < (n - 1) * stride + MASTER_KEY_LENGTH):
+        raise ValueError("master keys: n keys of 20 bytes, key_stride >= 20 bytes apart")
+    return master_key, stride
+
+
+def _package_v2(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key,
+                key_stride, flags, small_threshold, requests, request_offsets, align, stream, sync_check):
+    import torch
+    if algo is None:
+        raise NotImplementedError("DUMMY digests need no device work")
+    n = offsets.numel()
+    dev = payload.device
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    keys, stride = _master_keys(master_key, n, key_stride, lambda a: torch.from_numpy(a.copy()).to(dev))
+    if request_offsets is None:
+        request_offsets, total = request_offsets_v2(request_sizes_v2(algo, lengths, small_threshold), align)
+        if requests is None:  # (the one host sync of this path: pass `requests` or offsets to avoid it)
+            requests = torch.empty(int(total) if n else 0, dtype=torch.uint8, device=dev)
+    elif requests is None:
+        raise ValueError("request_offsets given without the requests buffer they index")
+    digests = torch.empty(n, dtype=torch.int32, device=dev)
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(lib().bkd_digest_package_batch_v2(
+            algo, ledger_id, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
+            _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n), _ck._dev_ptr(lacs, "lacs", i64, dev, n),
+            _ck._dev_ptr(length_fields, "length_fields", i64, dev, n), _ck._dev_ptr(payload, "payload"),
+            payload.numel() * payload.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
+            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(keys, "master_key", torch.uint8, dev),
+            stride, flags, small_threshold, _ck._dev_ptr(requests, "requests", torch.uint8, dev), requests.numel(),
+            _ck._dev_ptr(request_offsets, "request_offsets", i64, dev, n), _ck._dev_ptr(digests, "digests"), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+    return requests, request_offsets, digests
+
+
+def package_batch_v2(digest_type, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key,
+                     *, key_stride=None, flags: int = FLAG_NONE, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD,
+                     requests=None, request_offsets=None, align: int = 1, stream=None, sync_check: bool = False):
+    """``DigestManager.package_batch_v2`` with ledger_ids[i] (int64[n]) framing entry i."""
+    if ledger_ids is None:
+        raise ValueError("ledger_ids holds one ledger id per entry")
+    return _package_v2(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
+                       master_key, key_stride, flags, small_threshold, requests, request_offsets, align, stream,
+                       sync_check)
+
+
+def _package_v2_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key, key_stride,
+                     flags, small_threshold):
+    if algo is None:
+        raise NotImplementedError("DUMMY digests need no device work")
+    views = [_ck._host_view(p) for p in payloads]
+    n = len(views)
+    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
+    lac = np.ascontiguousarray(lacs, dtype=np.int64)
+    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
+    lids = None if ledger_ids is None else np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    if not (ids.size == lac.size == lf.size == n) or (lids is not None and lids.size != n):
+        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
+    if not isinstance(master_key, (bytes, bytearray, memoryview)):
+        master_key = np.ascontiguousarray(master_key, dtype=np.uint8)
+    keys, stride = _master_keys(master_key, n, key_stride)
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    offs, total = request_offsets_v2(request_sizes_v2(algo, lens, small_threshold))
+    buf = np.zeros(int(total) if n else 0, dtype=np.uint8)
+    rptr = (buf.ctypes.data + offs).astype(np.uint64)
+    digests = np.zeros(n, dtype=np.uint32)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_package_batch_v2_host(
+        algo, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(keys.ctypes.data), stride, flags,
+        small_threshold, vp(rptr.ctypes.data), vp(digests.ctypes.data)))
+    del views
+    ends = np.append(offs[1:], total) if n else offs
+    return [buf[a:b] for a, b in zip(offs.tolist(), ends.tolist())], digests
+
+
+def package_batch_v2_host(digest_type, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key, *,
+                          key_stride=None, flags: int = FLAG_NONE,
+                          small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD):
+    """``DigestManager.package_batch_v2_host`` with ledger_ids[i] framing entry i."""
+    if ledger_ids is None:
+        raise ValueError("ledger_ids holds one ledger id per entry")
+    return _package_v2_host(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key,
+                            key_stride, flags, small_threshold)
+
+
 class CRC32CDigestManager(DigestManager):
     """CRC32CDigestManager.java:27-62."""
     algo = CRC32C
@@ -603,3 +761,4 @@ class DummyDigestManager(DigestManager):
 
     verify_batch = package_batch_host = verify_batch_host = reframe_batch = reframe_batch_host = package_batch
     package_batch_segments = package_batch_segments_host = package_batch
+    package_batch_v2 = package_batch_v2_host = package_batch

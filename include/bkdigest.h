@@ -346,6 +346,53 @@ BKD_API int bkd_crc_batch_segments_host(int algo, const void* const* h_seg_ptrs,
                                         uint64_t nseg, const uint64_t* h_seg_first, uint64_t n,
                                         const uint32_t* h_seeds, uint32_t seed_all, uint32_t* h_out);
 
+/* ---- V2 add requests, packaged whole (the wire protocol Pulsar's brokers set) -----------------
+ * With useV2Protocol, computeDigestAndPackageForSending does not return [header][digest] beside the
+ * payload but one request buffer ($BK/proto/checksum/DigestManager.java:126-167):
+ *   [int32 BE  headersSize + payloadSize]   headersSize = 4 + 20 + 32 + mac (:130-134, :138)
+ *   [int32 BE  PacketHeader.toInt(CURRENT_PROTOCOL_VERSION = 2, ADDENTRY = 1, flags)]
+ *                                           (:139-141; $BK/proto/BookieProtocol.java:47, 75-83, 114)
+ *   [20 B      master key]                  (:142; MASTER_KEY_LENGTH, BookieProtocol.java:65)
+ *   [32 B      ledger id, entry id, LAC, length, BE]   (:146-149)
+ *   [mac B     digest = update(update(0, header), payload)]   (:152-155)
+ *   [payload]  only when it is shorter than SMALL_ENTRY_SIZE_THRESHOLD (:128, :160-163;
+ *              $BK/proto/BookieProtoEncoding.java:48); a larger payload follows the 60 + mac bytes as the
+ *              second buffer of a ByteBufList (:165), and is not copied.
+ * Request i is written at d_requests + d_request_offsets[i], at any alignment: 60 + mac bytes, and
+ * d_lengths[i] payload bytes behind them when d_lengths[i] < small_threshold. No other byte is written:
+ * not between requests, not behind the digest of an entry at or over the threshold. small_threshold is
+ * the caller's (BKD_V2_SMALL_ENTRY_THRESHOLD for the reference's; 0 copies nothing). The ledger id is
+ * d_ledger_ids[i], or ledger_id for all when d_ledger_ids is NULL; the length field is the caller's, as
+ * in bkd_digest_package_batch. Entry i's master key is the 20 bytes at d_master_keys + i*key_stride;
+ * key_stride == 0 is one key for all, key_stride in 1..19 and flags over 16 bits are
+ * BKD_ERR_INVALID_ARG. d_digests[i] receives the digest value. Requests must not overlap each other or
+ * the payload (the result is undefined otherwise).
+ * Device pointers; asynchronous on `stream`, no host synchronisation; n == 0 launches nothing. The
+ * digests come as bkd_digest_package_batch computes them; one kernel then writes every request's 60 +
+ * mac bytes and one copies the payloads under the threshold, a lane group per entry. An out-of-range
+ * payload gets digest 0, its 60 + mac bytes are still written, nothing is copied, and the stream's
+ * bounds flag is raised (BKD_ERR_BOUNDS from the next bkd_stream_sync); a request whose range does not
+ * lie inside requests_size is not written at all and raises the same flag; every other entry is exact. */
+#define BKD_V2_SMALL_ENTRY_THRESHOLD 16384u
+BKD_API int bkd_digest_package_batch_v2(int algo, int64_t ledger_id, const int64_t* d_ledger_ids,
+                                        const int64_t* d_entry_ids, const int64_t* d_lacs,
+                                        const int64_t* d_length_fields, const void* d_payload, uint64_t payload_size,
+                                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                        const uint8_t* d_master_keys, uint64_t key_stride, uint32_t flags,
+                                        uint32_t small_threshold, void* d_requests, uint64_t requests_size,
+                                        const uint64_t* d_request_offsets, uint32_t* d_digests, void* stream);
+/* Host-resident: payload i is its own host buffer, h_requests[i] the caller's buffer for request i —
+ * the allocator.buffer(bufferSize) of DigestManager.java:135-137, 60 + mac (+ h_lengths[i]) bytes.
+ * Synchronous; route by bkd_set_host_batch_route. CPU: DigestManager's arithmetic per entry on the
+ * host threads, the payload copied in right after it is folded; it needs no device. GPU: staged and
+ * digested as bkd_digest_package_batch_host; the host writes each prefix, the returned header and
+ * digest, and copies the small payloads from their sources, so no payload byte comes back over PCIe. */
+BKD_API int bkd_digest_package_batch_v2_host(int algo, int64_t ledger_id, const int64_t* h_ledger_ids,
+                                             const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                             const int64_t* h_length_fields, const void* const* h_payloads,
+                                             const uint32_t* h_lengths, uint64_t n, const uint8_t* h_master_keys,
+                                             uint64_t key_stride, uint32_t flags, uint32_t small_threshold,
+                                             void* const* h_requests, uint32_t* h_digests);
 /* ---- re-framing verified entries with a new LAC (re-replication) -----------------------
  * LedgerFragmentReplicator frames every entry it has just read and verified a second time with the
  * ledger's current LAC: computeDigestAndPackageForSending(entryId, lh.getLastAddConfirmed(),
