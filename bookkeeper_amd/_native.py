@@ -30,6 +30,8 @@ VERIFY_ENTRY_MISMATCH = 4
 REFRAME_TRUSTED = 1  # BKD_REFRAME_TRUSTED
 REQUEST_SKIP_ENTRY_ID = 1  # BKD_REQUEST_SKIP_ENTRY_ID
 V2_SMALL_ENTRY_THRESHOLD = 16384  # BKD_V2_SMALL_ENTRY_THRESHOLD
+MAC_MAX_ENTRY = 16 << 20  # BKD_MAC_MAX_ENTRY
+MAC_LENGTH = 20  # MacDigestManager.getMacCodeLength
 
 HEADER_PATH = os.path.join(ROOT, "include", "bkdigest.h")
 
@@ -96,6 +98,16 @@ PROTOTYPES = {
     "bkd_digest_reframe_batch": (_int, [_int, _i64, _i64, _int, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
                                         _vp, _vp, _vp]),
     "bkd_digest_reframe_batch_host": (_int, [_int, _i64, _i64, _int, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "bkd_mac_gen_digest": (_int, [_c.c_char_p, _vp, _u64, _vp]),
+    "bkd_mac_key_init": (_int, [_vp, _u64, _vp]),
+    "bkd_mac_key_state": (_int, [_vp, _u64, _vp]),
+    "bkd_mac_cpu": (_int, [_vp, _vp, _u64, _vp]),
+    "bkd_mac_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "bkd_digest_package_batch_mac": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "bkd_digest_verify_batch_mac": (_int, [_vp, _i64, _i64, _int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_mac_batch_host": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "bkd_digest_package_batch_mac_host": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64]),
+    "bkd_digest_verify_batch_mac_host": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_index": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_verify": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),

@@ -314,6 +314,95 @@ def crc_batch_segments_host(algo: int, segments, seg_first, seeds=None, seed_all
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# MAC ledgers: HMAC-SHA1 (MacDigestManager.java:46-107)
+# ---------------------------------------------------------------------------------------------
+
+MAC_LENGTH = 20
+
+
+def _key_ptr(key_state):
+    ks = np.ascontiguousarray(key_state, dtype=np.uint32)
+    if ks.size != 10:
+        raise ValueError("a MAC key state holds ten words (mac_key_init)")
+    return ks, ctypes.c_void_p(ks.ctypes.data)
+
+
+def mac_gen_digest(pad: bytes, passwd: bytes) -> bytes:
+    """SHA1(pad || passwd): MacDigestManager.genDigest (a ledger's master key with pad b"ledger")."""
+    out = np.zeros(MAC_LENGTH, dtype=np.uint8)
+    passwd = bytes(passwd)
+    check(lib().bkd_mac_gen_digest(bytes(pad), passwd or None, len(passwd),
+                                   ctypes.c_void_p(out.ctypes.data)))
+    return out.tobytes()
+
+
+def mac_key_init(passwd: bytes) -> np.ndarray:
+    """The key state of a MAC ledger with this password: uint32[10], the HMAC inner and outer states
+    for the key SHA1("mac" || passwd). Every MAC call takes it."""
+    ks = np.zeros(10, dtype=np.uint32)
+    passwd = bytes(passwd)
+    check(lib().bkd_mac_key_init(passwd or None, len(passwd),
+                                 ctypes.c_void_p(ks.ctypes.data)))
+    return ks
+
+
+def mac_key_state(key: bytes) -> np.ndarray:
+    """The key state of a raw HMAC-SHA1 key of at most 64 bytes (bkd_mac_key_state)."""
+    ks = np.zeros(10, dtype=np.uint32)
+    key = bytes(key)
+    check(lib().bkd_mac_key_state(key or None, len(key), ctypes.c_void_p(ks.ctypes.data)))
+    return ks
+
+
+def mac_cpu(key_state, buffer) -> bytes:
+    """HMAC of one host buffer on the CPU (bkd_mac_cpu): 20 bytes."""
+    ks, kp = _key_ptr(key_state)
+    view = _host_view(buffer)
+    out = np.zeros(MAC_LENGTH, dtype=np.uint8)
+    check(lib().bkd_mac_cpu(kp, ctypes.c_void_p(view.ctypes.data if view.size else 0), view.size,
+                            ctypes.c_void_p(out.ctypes.data)))
+    return out.tobytes()
+
+
+def mac_batch(key_state, base, offsets, lengths, out=None, stream=None, sync_check: bool = False):
+    """out[i] = HMAC(base[offsets[i] : offsets[i] + lengths[i]]) on the device, one lane per entry:
+    a uint8 tensor [n, 20]. An entry out of range or longer than MAC_MAX_ENTRY is not read, gets zeros
+    and makes the stream's next ``stream_sync`` raise BKD_ERR_BOUNDS (here, when ``sync_check``)."""
+    import torch
+    ks, kp = _key_ptr(key_state)
+    n = offsets.numel()
+    if lengths.numel() != n:
+        raise ValueError("offsets/lengths size mismatch")
+    dev = base.device
+    if out is None:
+        out = torch.empty((n, MAC_LENGTH), dtype=torch.uint8, device=dev)
+    with _on_device(base):
+        st = _stream_ptr(stream, base)
+        check(lib().bkd_mac_batch(kp, _dev_ptr(base, "base"), base.numel() * base.element_size(),
+                                  _dev_ptr(offsets, "offsets", torch.int64, dev),
+                                  _dev_ptr(lengths, "lengths", _u32_dtypes(), dev), n,
+                                  _dev_ptr(out, "out", torch.uint8, dev, n * MAC_LENGTH), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+    return out
+
+
+def mac_batch_host(key_state, entries) -> np.ndarray:
+    """HMAC of each host buffer of `entries`: uint8[n, 20]. Route by ``set_host_batch_route``; automatic
+    is the GPU whenever a device is visible (the CPU route for a batch with an entry over MAC_MAX_ENTRY)."""
+    ks, kp = _key_ptr(key_state)
+    views = [_host_view(e) for e in entries]
+    n = len(views)
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    out = np.zeros((n, MAC_LENGTH), dtype=np.uint8)
+    vp = ctypes.c_void_p
+    check(lib().bkd_mac_batch_host(kp, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(out.ctypes.data)))
+    del views
+    return out
+
+
 def fill_splitmix64(buf, seed: int, first_word: int = 0, stream=None) -> None:
     """Device-side synthetic input: little-endian splitmix64 words."""
     nbytes = buf.numel() * buf.element_size()

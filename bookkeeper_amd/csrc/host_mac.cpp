@@ -1,0 +1,159 @@
+// Host HMAC-SHA1 for MAC ledgers (host_mac.hpp): portable C++ over mac_sha1.hpp.
+#include "host_mac.hpp"
+
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "host_batch.hpp"
+#include "mac_sha1.hpp"
+
+namespace bkd {
+namespace host {
+
+namespace {
+
+inline uint32_t be32(const uint8_t* p) {
+    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+
+inline void put_be32(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+inline void put_be64(uint8_t* p, uint64_t v) {
+    put_be32(p, (uint32_t)(v >> 32));
+    put_be32(p + 4, (uint32_t)v);
+}
+
+// Continues h over the message pre[0, pre_len) || p[0, len) and finishes it: padding with the bit
+// length of prior_bytes + the message. Blocks that lie whole inside p are read in place; the others
+// (the prefix's, the tail's, the padding's) are built in a zeroed 64-byte buffer from the message's own
+// bytes and go through sha1::padded_word, as the device builds them in registers.
+void hash_message(uint32_t (&h)[5], const uint8_t* pre, uint64_t pre_len, const uint8_t* p, uint64_t len,
+                  uint64_t prior_bytes) {
+    const uint64_t m = pre_len + len;
+    const uint64_t padded = sha1::padded_bytes(m);
+    const uint64_t bits = (prior_bytes + m) * 8u;
+    uint32_t w[16];
+    for (uint64_t pos = 0; pos < padded; pos += 64u) {
+        if (pos >= pre_len && pos + 64u <= m) {
+            const uint8_t* q = p + (pos - pre_len);
+            for (int t = 0; t < 16; ++t) w[t] = be32(q + 4 * t);
+        } else {
+            uint8_t buf[64] = {0};
+            const uint64_t end = std::min(pos + 64u, m);
+            if (pos < pre_len) memcpy(buf, pre + pos, (size_t)(std::min(end, pre_len) - pos));
+            const uint64_t d0 = std::max(pos, pre_len);
+            if (end > d0) memcpy(buf + (d0 - pos), p + (d0 - pre_len), (size_t)(end - d0));
+            for (int t = 0; t < 16; ++t) w[t] = sha1::padded_word(be32(buf + 4 * t), pos + 4u * t, m, padded, bits);
+        }
+        sha1::compress(h, w);
+    }
+}
+
+// f(i) for i in [0, n), one entry per task from a shared counter over the host pool; small batches inline.
+template <class F>
+void each_entry(uint64_t n, const uint32_t* lens, F&& f) {
+    if (n == 0) return;
+    Pool& pool = Pool::get();
+    const int threads = pool.active();
+    uint64_t bytes = 0;
+    for (uint64_t i = 0; i < n && bytes < (1u << 16); ++i) bytes += lens[i] + 64u;
+    if (threads == 1 || n == 1 || bytes < (1u << 16)) {
+        for (uint64_t i = 0; i < n; ++i) f(i);
+        return;
+    }
+    std::atomic<uint64_t> next{0};
+    pool.run((int)std::min<uint64_t>((uint64_t)threads, n), [&](int) {
+        for (;;) {
+            const uint64_t i = next.fetch_add(1, std::memory_order_relaxed);
+            if (i >= n) return;
+            f(i);
+        }
+    });
+}
+
+}  // namespace
+
+void mac_gen_digest(const char* pad, const uint8_t* passwd, uint64_t passwd_len, uint8_t* out20) {
+    uint32_t h[5];
+    for (int k = 0; k < 5; ++k) h[k] = sha1::kInit[k];
+    hash_message(h, (const uint8_t*)pad, strlen(pad), passwd, passwd_len, 0);
+    for (int k = 0; k < 5; ++k) put_be32(out20 + 4 * k, h[k]);
+}
+
+void mac_key_state(const uint8_t* key, size_t key_len, uint32_t* key_state10) {
+    uint8_t block[64] = {0};
+    memcpy(block, key, std::min<size_t>(key_len, 64));
+    for (int half = 0; half < 2; ++half) {
+        const uint8_t x = half == 0 ? 0x36 : 0x5C;  // ipad, opad
+        uint32_t w[16], h[5];
+        for (int t = 0; t < 16; ++t) w[t] = be32(block + 4 * t) ^ (0x01010101u * x);
+        for (int k = 0; k < 5; ++k) h[k] = sha1::kInit[k];
+        sha1::compress(h, w);
+        for (int k = 0; k < 5; ++k) key_state10[5 * half + k] = h[k];
+    }
+}
+
+void mac_key_init(const uint8_t* passwd, uint64_t passwd_len, uint32_t* key_state10) {
+    uint8_t key[20];
+    mac_gen_digest("mac", passwd, passwd_len, key);
+    mac_key_state(key, sizeof(key), key_state10);
+}
+
+void mac_one(const uint32_t* key_state, const uint8_t* pre, uint32_t pre_len, const uint8_t* p, uint64_t len,
+             uint8_t* out20) {
+    uint32_t inner[5], mac[5];
+    for (int k = 0; k < 5; ++k) inner[k] = key_state[k];
+    hash_message(inner, pre, pre_len, p, len, 64);
+    sha1::hmac_outer(key_state + 5, inner, mac);
+    for (int k = 0; k < 5; ++k) put_be32(out20 + 4 * k, mac[k]);
+}
+
+void mac_list(const uint32_t* key_state, const uint8_t* const* ptrs, const uint32_t* lens, uint64_t n, uint8_t* out) {
+    each_entry(n, lens, [&](uint64_t i) { mac_one(key_state, nullptr, 0, ptrs[i], lens[i], out + i * kMacLen); });
+}
+
+uint64_t mac_verify_frames(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id, int id_checks,
+                           const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
+    each_entry(n, lens, [&](uint64_t i) {
+        const uint8_t* f = frames[i];
+        const uint32_t l = lens[i];
+        if (l < kMacFrameHead) {
+            status[i] = 1;
+            return;
+        }
+        uint8_t mac[kMacLen];
+        mac_one(key_state, f, 32, f + kMacFrameHead, l - kMacFrameHead, mac);
+        const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
+        const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
+        if (memcmp(mac, f + 32, kMacLen) != 0) status[i] = 2;
+        else if (lid != ledger_id) status[i] = 3;
+        else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) status[i] = 4;
+        else status[i] = 0;
+    });
+    for (uint64_t i = 0; i < n; ++i)
+        if (status[i] != 0) return i;
+    return n;
+}
+
+void mac_package_frames(const uint32_t* key_state, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
+                        const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                        uint64_t n, uint8_t* frames, uint64_t stride) {
+    each_entry(n, lens, [&](uint64_t i) {
+        uint8_t* f = frames + i * stride;
+        put_be64(f, (uint64_t)ledger_id);
+        put_be64(f + 8, (uint64_t)entry_ids[i]);
+        put_be64(f + 16, (uint64_t)lacs[i]);
+        put_be64(f + 24, (uint64_t)length_fields[i]);
+        mac_one(key_state, f, 32, payloads[i], lens[i], f + 32);
+    });
+}
+
+}  // namespace host
+}  // namespace bkd

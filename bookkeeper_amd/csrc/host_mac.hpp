@@ -1,0 +1,38 @@
+// The host side of the MAC digest type (MacDigestManager: HMAC-SHA1 keyed with SHA1("mac" || passwd),
+// $BK/proto/checksum/MacDigestManager.java:46-107): key setup, the per-call MAC, and the CPU route of
+// the host-resident MAC batches (one entry per task over the library's host pool, host_batch.hpp).
+// Portable C++ over mac_sha1.hpp, the arithmetic the device kernels share.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace bkd {
+namespace host {
+
+constexpr uint32_t kMacLen = 20;           // MacDigestManager.getMacCodeLength
+constexpr uint32_t kMacFrameHead = 32 + kMacLen;  // [32 B header][20 B mac]
+
+// out20 = SHA1(pad || passwd) (MacDigestManager.genDigest, :79-84); pad is a C string.
+void mac_gen_digest(const char* pad, const uint8_t* passwd, uint64_t passwd_len, uint8_t* out20);
+// key_state[0..4] / [5..9] = the SHA-1 states after compressing key ^ ipad / key ^ opad for an HMAC key
+// of at most 64 bytes; mac_key_init: key = SHA1("mac" || passwd) (:61).
+void mac_key_state(const uint8_t* key, size_t key_len, uint32_t* key_state10);
+void mac_key_init(const uint8_t* passwd, uint64_t passwd_len, uint32_t* key_state10);
+// out20 = HMAC over pre[0, pre_len) || p[0, len) (pre_len <= 64; the frame header, or nothing). No
+// byte at or past p + len is read.
+void mac_one(const uint32_t* key_state, const uint8_t* pre, uint32_t pre_len, const uint8_t* p, uint64_t len,
+             uint8_t* out20);
+// out + 20 i = HMAC(entry i), entry i its own buffer.
+void mac_list(const uint32_t* key_state, const uint8_t* const* ptrs, const uint32_t* lens, uint64_t n, uint8_t* out);
+// DigestManager.verifyDigest per frame [32 B header][20 B mac][payload] (DigestManager.java:226-283);
+// id_checks: 0 ledger + entry ids, 1 ledger id only. Returns the first failing index (n when none).
+uint64_t mac_verify_frames(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id, int id_checks,
+                           const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status);
+// The 32-byte BE header and the MAC of entry i into frames + i * stride (DigestManager.java:146-155,
+// 172-178); no other byte of the stride is written.
+void mac_package_frames(const uint32_t* key_state, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
+                        const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                        uint64_t n, uint8_t* frames, uint64_t stride);
+
+}  // namespace host
+}  // namespace bkd

@@ -5,7 +5,7 @@ Reference: bookkeeper-server/src/main/java/org/apache/bookkeeper/proto/checksum/
   CRC32CDigestManager.java:27-62 4-byte big-endian int digest via Crc32cIntChecksum
   CRC32DigestManager.java:28-87  8-byte big-endian long digest (zero-extended CRC32)
   DummyDigestManager.java:30-62  no digest
-HMAC (MacDigestManager) is HMAC-SHA1 arithmetic and outside this engine's scope.
+  MacDigestManager.java:46-107   20-byte HMAC-SHA1 keyed with SHA1("mac" || passwd)
 
 Per-entry methods keep the reference's two ``update`` calls (header, then payload). The batch
 methods (``package_batch`` / ``verify_batch``) are the new device path: one launch sequence
@@ -13,6 +13,7 @@ frames or verifies thousands of device-resident entries (SURVEY.md §8f rows 1-3
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import enum
 import struct
@@ -82,7 +83,7 @@ class DigestManager:
         if digestType == DigestType.DUMMY:
             return DummyDigestManager(ledgerId, useV2Protocol)
         if digestType == DigestType.HMAC:
-            raise NotImplementedError("HMAC-SHA1 digests are outside the GPU CRC engine (SURVEY.md §2)")
+            return MacDigestManager(ledgerId, passwd, useV2Protocol)
         raise ValueError(f"Unknown checksum type: {digestType}")
 
     # ---- the two hooks subclasses define (DigestManager.java:56-76) ----
@@ -762,3 +763,131 @@ class DummyDigestManager(DigestManager):
     verify_batch = package_batch_host = verify_batch_host = reframe_batch = reframe_batch_host = package_batch
     package_batch_segments = package_batch_segments_host = package_batch
     package_batch_v2 = package_batch_v2_host = package_batch
+
+
+class MacDigestManager(DigestManager):
+    """MacDigestManager.java:46-107: HmacSHA1 keyed with SHA1("mac" || passwd), a 20-byte digest.
+
+    The reference's stateful ``Mac`` (update per buffer, doFinal in populateValueAndReset, :86-101) maps
+    onto collecting the pieces of one entry: ``update`` returns the pieces seen so far and
+    ``digest_bytes`` finishes them through the library's CPU HMAC (bkd_mac_cpu); composite buffers are
+    joined. That is the latency-bound per-call path. The batch methods run one entry per GPU lane
+    (bkd_mac_batch and the two framed calls) or one entry per host task."""
+    algo = None
+    macCodeLength = 20
+
+    def __init__(self, ledgerId: int, passwd: bytes, useV2Protocol: bool = False):
+        super().__init__(ledgerId, useV2Protocol)
+        self.passwd = bytes(passwd)
+        self.key_state = _ck.mac_key_init(self.passwd)
+
+    @staticmethod
+    def genDigest(pad: str, passwd: bytes) -> bytes:  # :79-84
+        return _ck.mac_gen_digest(pad.encode(), passwd)
+
+    def internalUpdate(self, digest, buf, offset: int, length: int):
+        piece = bytes(memoryview(buf).cast("B")[offset:offset + length])
+        return (digest or ()) + (piece,)
+
+    def digest_bytes(self, digest) -> bytes:
+        return _ck.mac_cpu(self.key_state, b"".join(digest or ()))
+
+    def isInt32Digest(self) -> bool:
+        return False
+
+    # ---- batches ----
+    def package_batch(self, entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride=None,
+                      stream=None, sync_check: bool = False, out_frames=None):
+        """As ``DigestManager.package_batch`` with frames of [32 B header][20 B MAC] (``out_frames``: a
+        uint8 [n, frame_stride] device tensor to write them into, only 52 bytes of each row); returns
+        (frames[n, frame_stride] uint8, macs uint8[n, 20], a copy of the frames' MAC bytes). A payload
+        out of range or longer than MAC_MAX_ENTRY is not read: zero MAC, BKD_ERR_BOUNDS from the stream's
+        next sync (here, when ``sync_check``)."""
+        import torch
+        n = offsets.numel()
+        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
+        dev = payload.device
+        if out_frames is None:
+            out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+        elif out_frames.dim() != 2 or out_frames.shape[0] < n or out_frames.shape[1] != stride:
+            raise ValueError("out_frames must be a [n, frame_stride] tensor")
+        frames = out_frames
+        i64, u32 = torch.int64, _ck._u32_dtypes()
+        ks, kp = _ck._key_ptr(self.key_state)
+        with _ck._on_device(payload):
+            st = _ck._stream_ptr(stream, payload)
+            check(lib().bkd_digest_package_batch_mac(
+                kp, self.ledgerId, _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
+                _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
+                _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
+                _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
+                _ck._dev_ptr(frames, "frames", torch.uint8, dev), stride, st))
+            if sync_check:
+                check(lib().bkd_stream_sync(st))
+            with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+                macs = frames[:, METADATA_LENGTH:METADATA_LENGTH + self.macCodeLength].contiguous()
+        return frames, macs
+
+    def verify_batch(self, framed, offsets, lengths, first_entry_id: int, skip_entry_check: bool = False,
+                     stream=None):
+        """As ``DigestManager.verify_batch``: (status int32[n], first_bad int64[1])."""
+        import torch
+        n = offsets.numel()
+        dev = framed.device
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        first_bad = torch.empty(1, dtype=torch.int64, device=dev)
+        ks, kp = _ck._key_ptr(self.key_state)
+        with _ck._on_device(framed):
+            check(lib().bkd_digest_verify_batch_mac(
+                kp, self.ledgerId, first_entry_id, int(skip_entry_check), _ck._dev_ptr(framed, "framed"),
+                framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", torch.int64, dev),
+                _ck._dev_ptr(lengths, "lengths", _ck._u32_dtypes(), dev, n), n, _ck._dev_ptr(status, "status"),
+                _ck._dev_ptr(first_bad, "first_bad"), _ck._stream_ptr(stream, framed)))
+        return status, first_bad
+
+    def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
+        """As ``DigestManager.verify_batch_host``: (status int32[n], first_bad)."""
+        views = [_ck._host_view(f) for f in frames]
+        n = len(views)
+        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+        lens = np.array([v.size for v in views], dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        first_bad = ctypes.c_uint64(0)
+        ks, kp = _ck._key_ptr(self.key_state)
+        vp = ctypes.c_void_p
+        check(lib().bkd_digest_verify_batch_mac_host(
+            kp, self.ledgerId, first_entry_id, int(skip_entry_check), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n,
+            vp(status.ctypes.data), ctypes.byref(first_bad)))
+        del views
+        return status, int(first_bad.value)
+
+    def package_batch_host(self, entry_ids, lacs, length_fields, payloads, frame_stride=None):
+        """As ``DigestManager.package_batch_host``: (headers uint8[n, frame_stride] = [32 B header]
+        [20 B MAC], macs uint8[n, 20])."""
+        views = [_ck._host_view(p) for p in payloads]
+        n = len(views)
+        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
+        ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
+        lac = np.ascontiguousarray(lacs, dtype=np.int64)
+        lf = np.ascontiguousarray(length_fields, dtype=np.int64)
+        if not (ids.size == lac.size == lf.size == n):
+            raise ValueError("entry_ids, lacs, length_fields and payloads must have one element per entry")
+        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+        lens = np.array([v.size for v in views], dtype=np.uint32)
+        frames = np.zeros((n, stride), dtype=np.uint8)
+        ks, kp = _ck._key_ptr(self.key_state)
+        vp = ctypes.c_void_p
+        check(lib().bkd_digest_package_batch_mac_host(
+            kp, self.ledgerId, vp(ids.ctypes.data), vp(lac.ctypes.data), vp(lf.ctypes.data), vp(ptrs.ctypes.data),
+            vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride))
+        del views
+        return frames, frames[:, METADATA_LENGTH:METADATA_LENGTH + self.macCodeLength].copy()
+
+    def _no_batch(self, *a, **k):
+        raise NotImplementedError(
+            "MAC ledgers have package_batch / verify_batch and their _host forms only: HMAC has no affine "
+            "shortcut, so a reframe is a full re-hash, and composite and V2 batches are not built for MAC")
+
+    reframe_batch = reframe_batch_host = _no_batch
+    package_batch_segments = package_batch_segments_host = _no_batch
+    package_batch_v2 = package_batch_v2_host = _no_batch

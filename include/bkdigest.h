@@ -457,6 +457,66 @@ BKD_API int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, 
                         const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad,
                         void* stream);
 
+/* ---- MAC ledgers: batched HMAC-SHA1 (DigestType.MAC, MacDigestManager) ------------------
+ * MacDigestManager ($BK/proto/checksum/MacDigestManager.java:46-107) digests with HmacSHA1 keyed with
+ * SHA1("mac" || passwd) (:61, :79-84); the digest is 20 bytes (:67-69) written after the 32-byte header
+ * (DigestManager.java:146-155, 172-178). SHA-1 is serial inside an entry and entries are independent:
+ * the device kernels hash one entry per lane (mac_kernels.hpp), the CPU route one entry per host task.
+ *
+ * Key setup (host only, no device). gen_digest: out20 = SHA1(pad || passwd), MacDigestManager.genDigest
+ * — with pad "ledger" it is a ledger's master key (:48-55), with "mac" the HMAC key. key_init writes ten
+ * words: the SHA-1 state after compressing key ^ ipad (words 0..4) and key ^ opad (5..9) for
+ * key = SHA1("mac" || passwd). key_state: the same for a raw HMAC key of at most 64 bytes. Every MAC call
+ * takes the ten words as a host pointer and reads them during the call. */
+BKD_API int bkd_mac_gen_digest(const char* pad, const void* passwd, uint64_t passwd_len, uint8_t* out20);
+BKD_API int bkd_mac_key_init(const void* passwd, uint64_t passwd_len, uint32_t* key_state10);
+BKD_API int bkd_mac_key_state(const void* key, uint64_t key_len, uint32_t* key_state10);
+/* out20 = HMAC of one host buffer, always on the CPU (no device needed), any length. */
+BKD_API int bkd_mac_cpu(const uint32_t* key_state, const void* h_ptr, uint64_t len, uint8_t* out20);
+
+/* One lane hashes one entry serially, so an entry's length bounds the kernel's run time: the device
+ * calls refuse entries (verify: frames) longer than this. The reference's largest entry is its Netty
+ * frame limit, 5 MiB ($BK/conf/AbstractConfiguration.java:147). */
+#define BKD_MAC_MAX_ENTRY (16u << 20)
+
+/* Device-resident batches. Asynchronous on `stream`, no host synchronisation; n == 0 launches nothing
+ * (verify then writes 0 to *d_first_bad). Entries are indexed as in bkd_crc_batch, frames laid out and
+ * statuses decided as in bkd_digest_package_batch / bkd_digest_verify_batch with a 20-byte digest
+ * (frame_stride >= 52; only the 52 bytes of a stride are written; verify compares all 20 bytes of
+ * [0, 32) || [52, len)'s MAC, precedence too short, digest, ledger, entry). An entry with
+ * offset + length > size or length > BKD_MAC_MAX_ENTRY is not read: its MAC bytes are zero (the
+ * package call still writes its header), verify gives it BKD_VERIFY_TOO_SHORT, and the stream's bounds
+ * flag is raised (BKD_ERR_BOUNDS from the next bkd_stream_sync). Every load is an aligned dword that
+ * holds a byte of the entry: no byte outside [d_base, d_base + size) rounded out to dwords is read.
+ *   bkd_mac_batch: d_out + 20 i = HMAC(entry i). */
+BKD_API int bkd_mac_batch(const uint32_t* key_state, const void* d_base, uint64_t base_size, const uint64_t* d_offsets,
+                          const uint32_t* d_lengths, uint64_t n, uint8_t* d_out, void* stream);
+BKD_API int bkd_digest_package_batch_mac(const uint32_t* key_state, int64_t ledger_id, const int64_t* d_entry_ids,
+                                         const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                         uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                                         uint64_t n, void* d_frames, uint64_t frame_stride, void* stream);
+BKD_API int bkd_digest_verify_batch_mac(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id,
+                                        int skip_entry_check, const void* d_framed, uint64_t framed_size,
+                                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                        int32_t* d_status, uint64_t* d_first_bad, void* stream);
+/* Host-resident forms, shaped as their CRC siblings (entry i its own host buffer; package: 52 <=
+ * frame_stride <= 4096, only 52 bytes of a stride written). Synchronous. Route by
+ * bkd_set_host_batch_route: 1 the CPU route (one entry per task on the host threads; no device needed),
+ * 2 the GPU (pinned staging, then the kernels above), 0 automatic: the GPU whenever a device is visible
+ * — measured 41.8 GB/s against the CPU route's 7.9 GB/s on 16 threads, 64K entries of 4 KiB
+ * (DESIGN.md §5f). A batch that holds an entry over BKD_MAC_MAX_ENTRY takes the CPU route, or returns
+ * BKD_ERR_INVALID_ARG when the GPU is forced. */
+BKD_API int bkd_mac_batch_host(const uint32_t* key_state, const void* const* h_entries, const uint32_t* h_lengths,
+                               uint64_t n, uint8_t* h_out);
+BKD_API int bkd_digest_package_batch_mac_host(const uint32_t* key_state, int64_t ledger_id, const int64_t* h_entry_ids,
+                                              const int64_t* h_lacs, const int64_t* h_length_fields,
+                                              const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
+                                              void* h_frames, uint64_t frame_stride);
+BKD_API int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id,
+                                             int skip_entry_check, const void* const* h_frames,
+                                             const uint32_t* h_lengths, uint64_t n, int32_t* h_status,
+                                             uint64_t* h_first_bad);
+
 /* ---- synthetic input + test helpers --------------------------------------------------- */
 
 /* Fills nbytes of device memory with the little-endian splitmix64 stream
