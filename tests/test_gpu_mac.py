@@ -31,21 +31,7 @@ def sync():
     ck.stream_sync(torch.cuda.current_stream())
 
 
-def lay_out(entries, aligns, tail: int = 0):
-    """The entries in one buffer in order, entry i starting at the next byte whose address is aligns[i]
-    modulo 16 (None: back to back); the gaps and `tail` bytes behind the last entry hold 0xEE, which no
-    result may depend on. Returns (uint8 array, offsets int64, lengths int32)."""
-    parts, offs, at = [], [], 0
-    for e, a in zip(entries, aligns):
-        gap = 0 if a is None else (a - at) % 16
-        parts.append(b"\xEE" * gap)
-        at += gap
-        offs.append(at)
-        parts.append(e)
-        at += len(e)
-    parts.append(b"\xEE" * tail)
-    buf = np.frombuffer(b"".join(parts), dtype=np.uint8)
-    return buf, np.array(offs, dtype=np.int64), np.array([len(e) for e in entries], dtype=np.int32)
+lay_out = mu.lay_out
 
 
 def to_dev(gpu, *arrays):

@@ -162,6 +162,50 @@ def test_empty_batches(mgr, ks, cpu_route):
     assert ck.mac_batch_host(ks, []).shape == (0, 20)
 
 
+# ---- the fixtures of the GPU edge suite (test_gpu_mac_edges.py) through the CPU route ----
+
+@pytest.fixture(scope="module")
+def seg():
+    return mu.segment_batch()
+
+
+@pytest.fixture(scope="module")
+def seg_pk(seg):
+    return mu.segment_package(seg)
+
+
+def test_segment_batch_is_what_the_gpu_suite_assumes(seg):
+    assert len(seg["payloads"]) == 4551 and int(seg["lens"].max()) <= mu.SEGMENT
+    assert 181 * mu.MIB < int(seg["lens"].sum()) < 182 * mu.MIB
+    assert (seg["prefix"] > 2 * mu.SEGMENT).sum() >= 10  # entries that a third segment or a later one holds
+
+
+def test_segment_batch_mac_cpu_route(ks, cpu_route, seg):
+    mu.check_segment_mac(ck, ks, seg)
+
+
+@pytest.mark.parametrize("stride", [52, 60])
+def test_segment_batch_package_cpu_route(mgr, cpu_route, seg, seg_pk, stride):
+    mu.check_segment_package(mgr, seg, seg_pk, stride)
+
+
+def test_segment_batch_verify_cpu_route(mgr, cpu_route, seg):
+    for case in mu.segment_verify(seg)["cases"]:
+        mu.check_segment_verify(mgr, case)
+
+
+@pytest.mark.parametrize("ledger", mu.WIDE_LEDGERS)
+def test_wide_ids_cpu_route(cpu_route, ledger):
+    m = dg.DigestManager.instantiate(ledger, mu.PASSWD, dg.DigestType.HMAC)
+    w = mu.wide_ids()
+    heads, macs = m.package_batch_host(w["ids"], w["lacs"], w["lfs"], w["payloads"])
+    assert mu.wrong_rows(heads, w["heads"][ledger]) == []
+    assert (macs == heads[:, 32:]).all()
+    for name, frames, first, want in mu.wide_verify_cases(ledger):
+        status, fb = m.verify_batch_host(frames, first)
+        assert status.tolist() == want and fb == mu.first_bad(want), name
+
+
 # ---- MacDigestManager's per-entry methods ----
 
 def test_instantiate_hmac():
