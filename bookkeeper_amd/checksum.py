@@ -73,6 +73,26 @@ def _host_view(buf) -> np.ndarray:
     return np.frombuffer(memoryview(buf).cast("B"), dtype=np.uint8)
 
 
+def _host_entries(buffers, too_long: str | None = None):
+    """(views, pointers uint64[n] with 0 for an empty buffer, lengths uint32[n]) of a sequence of host buffers;
+    the views keep them alive across the call. `too_long`: the ValueError text for a buffer of 2^32 bytes or more."""
+    views = [_host_view(b) for b in buffers]
+    if too_long is not None and any(v.size >= 2**32 for v in views):
+        raise ValueError(too_long)
+    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
+    lens = np.array([v.size for v in views], dtype=np.uint32)
+    return views, ptrs, lens
+
+
+def _seeds_ptr(seeds, n: int):
+    """(the seeds of n host entries as a uint32 array to keep alive across the call, its pointer or null)."""
+    if seeds is not None:
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if seeds.size < n:
+            raise ValueError(f"seeds has {seeds.size} elements, needs {n}")
+    return seeds, ctypes.c_void_p(0 if seeds is None else seeds.ctypes.data)
+
+
 class GpuIntHash:
     """``IntHash`` implementation whose arithmetic runs in libbkdigest.so (JniIntHash.java:25-64)."""
 
@@ -265,12 +285,7 @@ def crc_batch_host(algo: int, base, offsets, lengths, seeds=None, seed_all: int 
     if lengths.size != n:
         raise ValueError("offsets/lengths size mismatch")
     out = np.zeros(n, dtype=np.uint32)
-    sp = ctypes.c_void_p(0)
-    if seeds is not None:
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
-        if seeds.size < n:
-            raise ValueError(f"seeds has {seeds.size} elements, needs {n}")
-        sp = ctypes.c_void_p(seeds.ctypes.data)
+    seeds, sp = _seeds_ptr(seeds, n)
     check(lib().bkd_crc_batch_host(algo, ctypes.c_void_p(view.ctypes.data if view.size else 0), view.size,
                                    ctypes.c_void_p(offsets.ctypes.data), ctypes.c_void_p(lengths.ctypes.data), n,
                                    sp, seed_all & 0xFFFFFFFF, ctypes.c_void_p(out.ctypes.data)))
@@ -280,14 +295,10 @@ def crc_batch_host(algo: int, base, offsets, lengths, seeds=None, seed_all: int 
 def _host_segments(segments, seg_first):
     """(views, pointers uint64[nseg], lengths uint32[nseg], seg_first uint64[n + 1], n) of host segments
     in CSR form, the sizes checked; the views keep the buffers alive across the call."""
-    views = [_host_view(s) for s in segments]
+    views, ptrs, lens = _host_entries(segments, "a segment holds fewer than 2^32 bytes")
     first = np.ascontiguousarray(seg_first, dtype=np.uint64)
     if first.ndim != 1 or first.size < 1:
         raise ValueError("seg_first holds n + 1 values")
-    if any(v.size >= 2**32 for v in views):
-        raise ValueError("a segment holds fewer than 2^32 bytes")
-    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-    lens = np.array([v.size for v in views], dtype=np.uint32)
     return views, ptrs, lens, first, first.size - 1
 
 
@@ -302,12 +313,7 @@ def crc_batch_segments_host(algo: int, segments, seg_first, seeds=None, seed_all
     views, ptrs, lens, first, n = _host_segments(segments, seg_first)
     out = np.zeros(n, dtype=np.uint32)
     vp = ctypes.c_void_p
-    sp = vp(0)
-    if seeds is not None:
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
-        if seeds.size < n:
-            raise ValueError(f"seeds has {seeds.size} elements, needs {n}")
-        sp = vp(seeds.ctypes.data)
+    seeds, sp = _seeds_ptr(seeds, n)
     check(lib().bkd_crc_batch_segments_host(algo, vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views),
                                             vp(first.ctypes.data), n, sp, seed_all & 0xFFFFFFFF, vp(out.ctypes.data)))
     del views
@@ -392,13 +398,10 @@ def mac_batch_host(key_state, entries) -> np.ndarray:
     """HMAC of each host buffer of `entries`: uint8[n, 20]. Route by ``set_host_batch_route``; automatic
     is the GPU whenever a device is visible (the CPU route for a batch with an entry over MAC_MAX_ENTRY)."""
     ks, kp = _key_ptr(key_state)
-    views = [_host_view(e) for e in entries]
-    n = len(views)
-    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-    lens = np.array([v.size for v in views], dtype=np.uint32)
-    out = np.zeros((n, MAC_LENGTH), dtype=np.uint8)
+    views, ptrs, lens = _host_entries(entries)
+    out = np.zeros((len(views), MAC_LENGTH), dtype=np.uint8)
     vp = ctypes.c_void_p
-    check(lib().bkd_mac_batch_host(kp, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(out.ctypes.data)))
+    check(lib().bkd_mac_batch_host(kp, vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(out.ctypes.data)))
     del views
     return out
 
@@ -411,30 +414,26 @@ def fill_splitmix64(buf, seed: int, first_word: int = 0, stream=None) -> None:
                                         _stream_ptr(stream, buf)))
 
 
+def _stream_call(name: str, stream) -> None:
+    """check(the library's `name`(stream)), with the stream's device current when `stream` is a torch stream."""
+    ptr, sdev, on_device = _stream_ptr(stream), getattr(stream, "device", None), contextlib.nullcontext()
+    if sdev is not None:
+        import torch
+        on_device = torch.cuda.device(sdev)
+    with on_device:
+        check(getattr(lib(), name)(ptr))
+
+
 def stream_sync(stream) -> None:
     """Waits for `stream` and raises BKD_ERR_BOUNDS if an indexed batch enqueued on it since its
     previous sync had an entry outside its base buffer (bkd_stream_sync; the flag is per stream)."""
-    ptr = _stream_ptr(stream)
-    sdev = getattr(stream, "device", None)
-    if sdev is not None:
-        import torch
-        with torch.cuda.device(sdev):
-            check(lib().bkd_stream_sync(ptr))
-    else:
-        check(lib().bkd_stream_sync(ptr))
+    _stream_call("bkd_stream_sync", stream)
 
 
 def release_stream(stream) -> None:
     """Waits for `stream` and frees the library's scratch for it (bkd_stream_release): call before a
     stream that ran indexed batches is dropped. Raises BKD_ERR_BOUNDS as a sync would."""
-    ptr = _stream_ptr(stream)
-    sdev = getattr(stream, "device", None)
-    if sdev is not None:
-        import torch
-        with torch.cuda.device(sdev):
-            check(lib().bkd_stream_release(ptr))
-    else:
-        check(lib().bkd_stream_release(ptr))
+    _stream_call("bkd_stream_release", stream)
 
 
 def cpu_resume(algo: int, current: int, buffer) -> int:

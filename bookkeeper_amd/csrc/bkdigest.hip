@@ -1501,22 +1501,39 @@ int check_host_segments(const void* const* h_seg_ptrs, const uint32_t* h_seg_len
     return BKD_OK;
 }
 
-// The GPU route of bkd_digest_package_batch_host, bkd_digest_package_batch_ledgers_host
-// (h_ledger_ids: one ledger id per entry, staged as a fourth aux array; else ledger_id for all) and
-// bkd_digest_package_batch_segments_host. stage(hs, s, i0, cnt, bytes) puts entries [i0, i0 + cnt)
-// back to back into slot s (entry_buffers, HostSegments); h_lengths[i] = entry i's bytes.
+// A null entry pointer is legal only for an empty entry; `noun` is what the form calls its entries.
+int check_host_entries(const char* noun, const void* const* ptrs, const uint32_t* lens, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (lens[i] && !ptrs[i]) return fail(BKD_ERR_INVALID_ARG, std::string("null ") + noun + " " + std::to_string(i));
+    return BKD_OK;
+}
+
+// A frame's `head` = 32 + digest length bytes fit frame_stride; bounded (the host-resident forms, whose
+// GPU route lands the frames in the kAux-byte staging buffers): and frame_stride is at most 4096.
+int check_frame_stride(uint64_t head, uint64_t frame_stride, bool bounded) {
+    if (bounded && (frame_stride < head || frame_stride > 4096u))
+        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
+    return frame_stride < head ? fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length") : BKD_OK;
+}
+
+// The GPU route of the host-resident package forms, CRC and MAC (h_ledger_ids: one ledger id per entry,
+// staged as a fourth aux array; else the launch's one ledger for all). stage(hs, s, i0, cnt, bytes) puts
+// entries [i0, i0 + cnt) back to back into slot s (entry_buffers, HostSegments); h_lengths[i] = entry i's bytes.
+// launch(ds, hs, s, d_ids, d_ledger_ids, cnt, bytes, dev_stride) enqueues the device sequence over slot s
+// (crc_package, bkd_digest_package_batch_mac_host's): entry ids, LACs and length fields at d_ids, d_ids + cnt,
+// d_ids + 2 * cnt, frame j to d_frm + j * dev_stride, digests (if it makes any: `digests`) to d_res.
 // out(frames, digests, i0, cnt) takes a finished segment's results from the pinned landing buffers:
-// frame j of entries [i0, i0 + cnt) at frames + j*frame_stride (host_frames: into the caller's frame
-// array; bkd_digest_package_batch_v2_host: into its requests).
-template <class Stage, class Out>
-int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
-                        const int64_t* h_lacs, const int64_t* h_length_fields, const Stage& stage,
-                        const uint32_t* h_lengths, uint64_t n, uint64_t frame_stride, const Out& out) {
+// frame j of entries [i0, i0 + cnt) at frames + j * dev_stride (host_frames: into the caller's frame array;
+// bkd_digest_package_batch_v2_host: into its requests).
+template <class Stage, class Launch, class Out>
+int package_host_staged(const int64_t* h_ledger_ids, const int64_t* h_entry_ids, const int64_t* h_lacs,
+                        const int64_t* h_length_fields, const Stage& stage, const uint32_t* h_lengths, uint64_t n,
+                        const Launch& launch, uint64_t dev_stride, bool digests, const Out& out) {
     StagedCall call(&HostStage::init_package);
     if (call.rc) return call.rc;
     HostStage& hs = **call.lease;
     const uint64_t fields = h_ledger_ids ? 4 : 3;
-    const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / frame_stride);
+    const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / dev_stride);
     auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
         const hipStream_t st = hs.st[s];
         int r = stage(hs, s, i0, cnt, bytes);
@@ -1528,12 +1545,10 @@ int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids
         if (h_ledger_ids) memcpy(aux + 3 * cnt, h_ledger_ids + i0, cnt * 8);
         BKD_HIP(hipMemcpyAsync(hs.d_aux[s], aux, cnt * 8 * fields, hipMemcpyHostToDevice, st));
         const int64_t* d_aux = reinterpret_cast<const int64_t*>(hs.d_aux[s]);
-        r = package_framed(*call.ds, st, algo, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
-                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], frame_stride, hs.d_res[s],
-                           h_ledger_ids ? d_aux + 3 * cnt : nullptr);
+        r = launch(*call.ds, hs, s, d_aux, h_ledger_ids ? d_aux + 3 * cnt : nullptr, cnt, bytes, dev_stride);
         if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * frame_stride, hipMemcpyDeviceToHost, st));
-        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * dev_stride, hipMemcpyDeviceToHost, st));
+        if (digests) BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
         return BKD_OK;
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
@@ -1543,18 +1558,54 @@ int package_host_staged(int algo, int64_t ledger_id, const int64_t* h_ledger_ids
     return host_segments(hs, h_lengths, n, max_entries, seg, drain);
 }
 
-// package_host_staged's `out` for the calls that return a frame array and the digests.
-auto host_frames(int algo, void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
+// package_host_staged's `launch` of the CRC forms.
+auto crc_package(int algo, int64_t ledger_id) {
+    return [=](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids, uint64_t cnt,
+               uint64_t bytes, uint64_t stride) {
+        return package_framed(ds, hs.st[s], algo, ledger_id, d_ids, d_ids + cnt, d_ids + 2 * cnt, hs.d_buf[s], bytes,
+                              hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride, hs.d_res[s], d_ledger_ids);
+    };
+}
+
+// package_host_staged's `out` for the calls that return a frame array (and the digests, unless h_digests
+// is null): each frame's `hl` = 32 + mac bytes, `src_stride` apart where they landed.
+auto host_frames(uint64_t hl, uint64_t src_stride, void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
     return [=](const uint8_t* frm, const uint32_t* res, uint64_t i0, uint64_t cnt) {
         // packed frames in one copy; with a wider stride only each frame's 32 + mac bytes (the bytes
         // between frames are the caller's, and the device never wrote them)
-        const uint64_t hl = 32u + mac_len(algo);
         uint8_t* dst = (uint8_t*)h_frames + i0 * frame_stride;
-        if (frame_stride == hl) memcpy(dst, frm, cnt * hl);
+        if (frame_stride == hl && src_stride == hl) memcpy(dst, frm, cnt * hl);
         else
-            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, frm + j * frame_stride, hl);
-        memcpy(h_digests + i0, res, cnt * 4);
+            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, frm + j * src_stride, hl);
+        if (h_digests) memcpy(h_digests + i0, res, cnt * 4);
     };
+}
+
+// The GPU route of bkd_digest_verify_batch_host and bkd_digest_verify_batch_mac_host.
+// launch(ds, hs, s, i0, cnt, bytes) enqueues the verify sequence over slot s's staged frames, entries
+// [i0, i0 + cnt): statuses to d_res, the segment's first_bad to d_fb. *h_first_bad: n on entry.
+template <class Launch>
+int verify_host_staged(const Launch& launch, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                       int32_t* h_status, uint64_t* h_first_bad) {
+    StagedCall call(&HostStage::init_verify);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        const hipStream_t st = hs.st[s];
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        r = launch(*call.ds, hs, s, i0, cnt, bytes);
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        BKD_HIP(hipMemcpyAsync(hs.h_fb[s], hs.d_fb[s], 8, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
+        merge_first_bad(hs, s, i0, cnt, h_first_bad);
+        return BKD_OK;
+    };
+    return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
 }
 
 // ---- MAC ledgers (HMAC-SHA1): one lane per entry (mac_kernels.hpp) ---------------------------------
@@ -1632,12 +1683,6 @@ int mac_host_route(const uint32_t* lengths, uint64_t n) {
                                                           " is longer than BKD_MAC_MAX_ENTRY (GPU route forced)")
                           : 1;
     return 2;
-}
-
-int check_host_entries(const void* const* ptrs, const uint32_t* lens, uint64_t n) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (lens[i] && !ptrs[i]) return fail(BKD_ERR_INVALID_ARG, "null entry " + std::to_string(i));
-    return BKD_OK;
 }
 
 }  // namespace
@@ -2037,11 +2082,10 @@ int bkd_digest_package_batch(int algo, int64_t ledger_id, const int64_t* d_entry
                              const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, void* d_frames,
                              uint64_t frame_stride, uint32_t* d_digests, void* stream) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_frames || !d_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    if (int rc = check_frame_stride(32u + mac_len(algo), frame_stride, false)) return rc;
     Call call(stream);
     if (call.rc) return call.rc;
     return package_framed(*call.ds, call.st, algo, ledger_id, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
@@ -2068,12 +2112,11 @@ int bkd_digest_package_batch_ledgers(int algo, const int64_t* d_ledger_ids, cons
                                      uint64_t n, void* d_frames, uint64_t frame_stride, uint32_t* d_digests,
                                      void* stream) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!d_ledger_ids || !d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_frames ||
         !d_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    if (int rc = check_frame_stride(32u + mac_len(algo), frame_stride, false)) return rc;
     Call call(stream);
     if (call.rc) return call.rc;
     return package_framed(*call.ds, call.st, algo, 0, d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size,
@@ -2107,37 +2150,22 @@ int bkd_digest_verify_batch_host(int algo, int64_t ledger_id, int64_t first_entr
     *h_first_bad = n;
     if (n == 0) return BKD_OK;
     if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
+    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
     const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
+    const int id_checks = skip_entry_check ? 1 : 0;
     if (route == 1) {
-        *h_first_bad = bkd::host::verify_frames(algo, ledger_id, first_entry_id, skip_entry_check ? 1 : 0,
+        *h_first_bad = bkd::host::verify_frames(algo, ledger_id, first_entry_id, id_checks,
                                                 (const uint8_t* const*)h_frames, h_lengths, n, h_status);
         return BKD_OK;
     }
-    StagedCall call(&HostStage::init_verify);
-    if (call.rc) return call.rc;
-    HostStage& hs = **call.lease;
-    const int id_checks = skip_entry_check ? 1 : 0;
-    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        uint64_t* d_fb = hs.d_fb[s];
-        r = verify_framed(*call.ds, st, algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s], bytes,
-                          hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), d_fb);
-        if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
-        BKD_HIP(hipMemcpyAsync(hs.h_fb[s], d_fb, 8, hipMemcpyDeviceToHost, st));
-        return BKD_OK;
-    };
-    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        merge_first_bad(hs, s, i0, cnt, h_first_bad);
-        return BKD_OK;
-    };
-    return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
+    return verify_host_staged(
+        [&](DeviceState& ds, HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) {
+            return verify_framed(ds, hs.st[s], algo, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s],
+                                 bytes, hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]),
+                                 hs.d_fb[s]);
+        },
+        h_frames, h_lengths, n, h_status, h_first_bad);
 }
 
 int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_entry_ids, const int64_t* h_lacs,
@@ -2145,14 +2173,12 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   const uint32_t* h_lengths, uint64_t n, void* h_frames, uint64_t frame_stride,
                                   uint32_t* h_digests) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
+    const uint64_t hl = 32u + mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_frames || !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < 32u + mac || frame_stride > 4096u)
-        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    if (int rc = check_host_entries("payload", h_payloads, h_lengths, n)) return rc;
     const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
@@ -2161,9 +2187,9 @@ int bkd_digest_package_batch_host(int algo, int64_t ledger_id, const int64_t* h_
                                   h_digests);
         return BKD_OK;
     }
-    return package_host_staged(algo, ledger_id, nullptr, h_entry_ids, h_lacs, h_length_fields,
-                               entry_buffers(h_payloads, h_lengths), h_lengths, n, frame_stride,
-                               host_frames(algo, h_frames, frame_stride, h_digests));
+    return package_host_staged(nullptr, h_entry_ids, h_lacs, h_length_fields, entry_buffers(h_payloads, h_lengths),
+                               h_lengths, n, crc_package(algo, ledger_id), frame_stride, true,
+                               host_frames(hl, frame_stride, h_frames, frame_stride, h_digests));
 }
 
 int bkd_digest_package_batch_v2(int algo, int64_t ledger_id, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
@@ -2199,7 +2225,7 @@ int bkd_digest_package_batch_v2_host(int algo, int64_t ledger_id, const int64_t*
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_master_keys || !h_requests ||
         !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    for (uint64_t i = 0; i < n; ++i) {
+    for (uint64_t i = 0; i < n; ++i) {  // (not check_host_entries: the first fault of either kind is the one named)
         if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
         if (!h_requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
     }
@@ -2216,8 +2242,8 @@ int bkd_digest_package_batch_v2_host(int algo, int64_t ledger_id, const int64_t*
     // GPU: staged and digested as bkd_digest_package_batch_host; each finished segment's packed frames
     // go into the requests behind the prefix the host writes, the small payloads from their sources
     const uint64_t hl = 32u + mac_len(algo);
-    return package_host_staged(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
-                               entry_buffers(h_payloads, h_lengths), h_lengths, n, hl,
+    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, entry_buffers(h_payloads, h_lengths),
+                               h_lengths, n, crc_package(algo, ledger_id), hl, true,
                                [&](const uint8_t* frm, const uint32_t* res, uint64_t i0, uint64_t cnt) {
                                    bkd::host::finish_requests_v2(algo, frm, payloads + i0, h_lengths + i0, cnt, head, i0,
                                                                  requests + i0, copy_threads());
@@ -2243,8 +2269,7 @@ int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const
     for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
     if (n == 0) return BKD_OK;
     if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
+    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
     const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     // the requests as per-entry expectations: what the CPU route checks frame by frame and what the
@@ -2313,15 +2338,13 @@ int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids,
                                           const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
                                           void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
+    const uint64_t hl = 32u + mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!h_ledger_ids || !h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_frames ||
         !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < 32u + mac || frame_stride > 4096u)
-        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    if (int rc = check_host_entries("payload", h_payloads, h_lengths, n)) return rc;
     const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
@@ -2330,9 +2353,9 @@ int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids,
                                           frame_stride, h_digests);
         return BKD_OK;
     }
-    return package_host_staged(algo, 0, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
-                               entry_buffers(h_payloads, h_lengths), h_lengths, n, frame_stride,
-                               host_frames(algo, h_frames, frame_stride, h_digests));
+    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, entry_buffers(h_payloads, h_lengths),
+                               h_lengths, n, crc_package(algo, 0), frame_stride, true,
+                               host_frames(hl, frame_stride, h_frames, frame_stride, h_digests));
 }
 
 int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id, int skip_entry_check, uint32_t flags,
@@ -2348,7 +2371,7 @@ int bkd_digest_reframe_batch(int algo, int64_t ledger_id, int64_t first_entry_id
     if (n && !d_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
     const uint32_t mac = mac_len(algo);
     if (n && d_out_frames) {
-        if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+        if (int rc = check_frame_stride(32u + mac, frame_stride, false)) return rc;
         const uint64_t fr0 = (uint64_t)(uintptr_t)d_out_frames, fr1 = fr0 + (n - 1u) * frame_stride + 32u + mac;
         const uint64_t in0 = (uint64_t)(uintptr_t)d_framed, in1 = in0 + framed_size;
         if (fr0 < in1 && in0 < fr1) return fail(BKD_ERR_INVALID_ARG, "out_frames overlaps the framed buffer");
@@ -2371,8 +2394,7 @@ int bkd_digest_reframe_batch_host(int algo, int64_t ledger_id, int64_t first_ent
     if (n == 0) return BKD_OK;
     if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (!h_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_lengths[i] && !h_frames[i]) return fail(BKD_ERR_INVALID_ARG, "null frame " + std::to_string(i));
+    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
     const bool trusted = (flags & BKD_REFRAME_TRUSTED) != 0;
     const int id_checks = skip_entry_check ? 1 : 0;
     const int route = framed_host_route(h_lengths, n);
@@ -2462,7 +2484,7 @@ int bkd_digest_package_batch_mac(const uint32_t* key_state, int64_t ledger_id, c
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_frames)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < bkd::host::kMacFrameHead) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    if (int rc = check_frame_stride(bkd::host::kMacFrameHead, frame_stride, false)) return rc;
     if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
     Call call(stream);
     if (call.rc) return call.rc;
@@ -2490,8 +2512,7 @@ int bkd_mac_batch_host(const uint32_t* key_state, const void* const* h_entries, 
     if (!key_state) return fail(BKD_ERR_INVALID_ARG, "null key state");
     if (n == 0) return BKD_OK;
     if (!h_entries || !h_lengths || !h_out) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    int rc = check_host_entries(h_entries, h_lengths, n);
-    if (rc) return rc;
+    if (int rc = check_host_entries("entry", h_entries, h_lengths, n)) return rc;
     const int route = mac_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
@@ -2525,10 +2546,8 @@ int bkd_digest_package_batch_mac_host(const uint32_t* key_state, int64_t ledger_
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_frames)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
     constexpr uint64_t hl = bkd::host::kMacFrameHead;
-    if (frame_stride < hl || frame_stride > 4096u)
-        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
-    int rc = check_host_entries(h_payloads, h_lengths, n);
-    if (rc) return rc;
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    if (int rc = check_host_entries("entry", h_payloads, h_lengths, n)) return rc;
     const int route = mac_host_route(h_lengths, n);
     if (route < 0) return route;
     if (route == 1) {
@@ -2536,35 +2555,14 @@ int bkd_digest_package_batch_mac_host(const uint32_t* key_state, int64_t ledger_
                                       (const uint8_t* const*)h_payloads, h_lengths, n, (uint8_t*)h_frames, frame_stride);
         return BKD_OK;
     }
-    StagedCall call(&HostStage::init_package);
-    if (call.rc) return call.rc;
-    HostStage& hs = **call.lease;
-    // the device writes packed 52-byte frames; the host puts each at its stride
-    const uint64_t max_entries = std::min<uint64_t>(HostStage::kSegEntries, HostStage::kAux / hl);
-    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        int64_t* aux = reinterpret_cast<int64_t*>(hs.h_aux[s]);
-        memcpy(aux, h_entry_ids + i0, cnt * 8);
-        memcpy(aux + cnt, h_lacs + i0, cnt * 8);
-        memcpy(aux + 2 * cnt, h_length_fields + i0, cnt * 8);
-        BKD_HIP(hipMemcpyAsync(hs.d_aux[s], aux, cnt * 24, hipMemcpyHostToDevice, st));
-        const int64_t* d_aux = reinterpret_cast<const int64_t*>(hs.d_aux[s]);
-        r = mac_package(*call.ds, st, key_state, ledger_id, d_aux, d_aux + cnt, d_aux + 2 * cnt, hs.d_buf[s], bytes,
-                        hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], hl);
-        if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * hl, hipMemcpyDeviceToHost, st));
-        return BKD_OK;
+    // the device writes packed 52-byte frames and no digest words; the host puts each frame at its stride
+    auto launch = [=](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t*, uint64_t cnt,
+                      uint64_t bytes, uint64_t stride) {
+        return mac_package(ds, hs.st[s], key_state, ledger_id, d_ids, d_ids + cnt, d_ids + 2 * cnt, hs.d_buf[s], bytes,
+                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
     };
-    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        uint8_t* dst = (uint8_t*)h_frames + i0 * frame_stride;
-        if (frame_stride == hl) memcpy(dst, hs.h_frm[s], cnt * hl);
-        else
-            for (uint64_t j = 0; j < cnt; ++j) memcpy(dst + j * frame_stride, hs.h_frm[s] + j * hl, hl);
-        return BKD_OK;
-    };
-    return host_segments(hs, h_lengths, n, max_entries, seg, drain);
+    return package_host_staged(nullptr, h_entry_ids, h_lacs, h_length_fields, entry_buffers(h_payloads, h_lengths),
+                               h_lengths, n, launch, hl, false, host_frames(hl, hl, h_frames, frame_stride, nullptr));
 }
 
 int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id,
@@ -2575,8 +2573,7 @@ int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t ledger_i
     *h_first_bad = n;
     if (n == 0) return BKD_OK;
     if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    int rc = check_host_entries(h_frames, h_lengths, n);
-    if (rc) return rc;
+    if (int rc = check_host_entries("entry", h_frames, h_lengths, n)) return rc;
     const int route = mac_host_route(h_lengths, n);
     if (route < 0) return route;
     const int id_checks = skip_entry_check ? 1 : 0;
@@ -2585,26 +2582,12 @@ int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t ledger_i
                                                     (const uint8_t* const*)h_frames, h_lengths, n, h_status);
         return BKD_OK;
     }
-    StagedCall call(&HostStage::init_verify);
-    if (call.rc) return call.rc;
-    HostStage& hs = **call.lease;
-    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        r = mac_verify(*call.ds, st, key_state, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s], bytes,
-                       hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), hs.d_fb[s]);
-        if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
-        BKD_HIP(hipMemcpyAsync(hs.h_fb[s], hs.d_fb[s], 8, hipMemcpyDeviceToHost, st));
-        return BKD_OK;
-    };
-    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        merge_first_bad(hs, s, i0, cnt, h_first_bad);
-        return BKD_OK;
-    };
-    return host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
+    return verify_host_staged(
+        [&](DeviceState& ds, HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) {
+            return mac_verify(ds, hs.st[s], key_state, ledger_id, first_entry_id + (int64_t)i0, id_checks, hs.d_buf[s],
+                              bytes, hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), hs.d_fb[s]);
+        },
+        h_frames, h_lengths, n, h_status, h_first_bad);
 }
 
 int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
@@ -2656,13 +2639,12 @@ int bkd_digest_package_batch_segments(int algo, int64_t ledger_id, const int64_t
                                       const uint32_t* d_seg_lengths, uint64_t nseg, const uint64_t* d_seg_first, uint64_t n,
                                       void* d_frames, uint64_t frame_stride, uint32_t* d_digests, void* stream) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_seg_first || !d_frames || !d_digests ||
         (nseg && (!d_seg_offsets || !d_seg_lengths)))
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (nseg && !d_payload && payload_size) return fail(BKD_ERR_INVALID_ARG, "null payload");
-    if (frame_stride < 32u + mac) return fail(BKD_ERR_INVALID_ARG, "frame_stride < 32 + digest length");
+    if (int rc = check_frame_stride(32u + mac_len(algo), frame_stride, false)) return rc;
     Call call(stream);
     if (call.rc) return call.rc;
     return package_segments(*call.ds, call.st, algo, ledger_id, d_ledger_ids, d_entry_ids, d_lacs, d_length_fields,
@@ -2676,14 +2658,12 @@ int bkd_digest_package_batch_segments_host(int algo, int64_t ledger_id, const in
                                            const uint32_t* h_seg_lengths, uint64_t nseg, const uint64_t* h_seg_first,
                                            uint64_t n, void* h_frames, uint64_t frame_stride, uint32_t* h_digests) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    const uint32_t mac = mac_len(algo);
+    const uint64_t hl = 32u + mac_len(algo);
     if (n == 0) return BKD_OK;
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_frames || !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (frame_stride < 32u + mac || frame_stride > 4096u)
-        return fail(BKD_ERR_INVALID_ARG, "frame_stride must be in [32 + digest length, 4096]");
-    int rc = check_host_segments(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
-    if (rc) return rc;
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    if (int rc = check_host_segments(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n)) return rc;
     const HostSegments segs(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
     const int route = framed_host_route(segs.entry_len.data(), n);
     if (route < 0) return route;
@@ -2693,9 +2673,9 @@ int bkd_digest_package_batch_segments_host(int algo, int64_t ledger_id, const in
                                            segs.entry_len.data(), n, (uint8_t*)h_frames, frame_stride, h_digests);
         return BKD_OK;
     }
-    return package_host_staged(algo, ledger_id, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, segs,
-                               segs.entry_len.data(), n, frame_stride,
-                               host_frames(algo, h_frames, frame_stride, h_digests));
+    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, segs, segs.entry_len.data(), n,
+                               crc_package(algo, ledger_id), frame_stride, true,
+                               host_frames(hl, frame_stride, h_frames, frame_stride, h_digests));
 }
 
 int bkd_crc_batch_segments_host(int algo, const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths, uint64_t nseg,

@@ -64,6 +64,68 @@ def _header(ledger_id: int, entry_id: int, lac: int, length: int) -> bytes:
     return struct.pack(">qqqq", ledger_id, entry_id, lac, length)
 
 
+def _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids=None, optional_ledgers: bool = False):
+    """The per-entry header fields of a host batch of n entries as contiguous int64 arrays: (entry ids,
+    LACs, length fields, ledger ids or None). The ValueError for a size mismatch names ledger_ids when
+    they are given, or when the form takes them optionally (`optional_ledgers`: the composite and V2 forms)."""
+    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
+    lac = np.ascontiguousarray(lacs, dtype=np.int64)
+    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
+    lids = None if ledger_ids is None else np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    if not (ids.size == lac.size == lf.size == n) or (lids is not None and lids.size != n):
+        raise ValueError(("ledger_ids, " if lids is not None or optional_ledgers else "") +
+                         "entry_ids, lacs, length_fields and payloads must have one element per entry")
+    return ids, lac, lf, lids
+
+
+def _package_frames(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride,
+                    out_frames, stream, sync_check, with_digests: bool = True):
+    """The device forms that frame one payload range per entry: the library's `fn`(*first, *ledger ids,
+    entry ids, ..., frames, stride, [digests,] stream); `ledger_ids` is () for a form of one ledger, the
+    (tensor,) for the many-ledger form. Returns (frames, digests int32[n] or None)."""
+    import torch
+    n = offsets.numel()
+    stride = frame_stride or (METADATA_LENGTH + mac)
+    dev = payload.device
+    if out_frames is None:
+        out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    elif out_frames.dim() != 2 or out_frames.shape[0] < n or out_frames.shape[1] != stride:
+        raise ValueError("out_frames must be a [n, frame_stride] tensor")
+    digests = torch.empty(n, dtype=torch.int32, device=dev) if with_digests else None
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(getattr(lib(), fn)(
+            *first, *(_ck._dev_ptr(t, "ledger_ids", i64, dev, n) for t in ledger_ids),
+            _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n), _ck._dev_ptr(lacs, "lacs", i64, dev, n),
+            _ck._dev_ptr(length_fields, "length_fields", i64, dev, n), _ck._dev_ptr(payload, "payload"),
+            payload.numel() * payload.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
+            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(out_frames, "frames", torch.uint8, dev), stride,
+            *((_ck._dev_ptr(digests, "digests"),) if with_digests else ()), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+    return out_frames, digests
+
+
+def _package_frames_host(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride,
+                         with_digests: bool = True):
+    """The host forms that frame one buffer per entry: the library's `fn`(*first, [ledger ids,] entry ids,
+    ..., frames, stride[, digests]). Returns (frames uint8[n, frame_stride], digests uint32[n] or None)."""
+    views, ptrs, lens = _ck._host_entries(payloads)
+    n = len(views)
+    stride = frame_stride or (METADATA_LENGTH + mac)
+    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids)
+    frames = np.zeros((n, stride), dtype=np.uint8)
+    digests = np.zeros(n, dtype=np.uint32) if with_digests else None
+    vp = ctypes.c_void_p
+    check(getattr(lib(), fn)(
+        *first, *(() if lids is None else (vp(lids.ctypes.data),)), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride,
+        *((vp(digests.ctypes.data),) if with_digests else ())))
+    del views
+    return frames, digests
+
+
 class DigestManager:
     algo: int | None = None
     macCodeLength: int = 0
@@ -161,6 +223,13 @@ class DigestManager:
             raise BKDigestMatchException(VERIFY_LEDGER_MISMATCH)
         return lac
 
+    # ---- what a digest type's batch methods pass to the library ----
+    _c_suffix = ""  # bkd_digest_verify_batch<suffix>[_host], bkd_digest_package_batch<suffix>[_host]
+
+    def _c_first(self):
+        """(the first C argument of those functions, what must stay alive while it is used)."""
+        return self.algo, None
+
     # ---- batch device path (new) ----
     def package_batch(self, entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride=None,
                       stream=None, sync_check: bool = False):
@@ -168,24 +237,9 @@ class DigestManager:
         frames[i] = [32 B header][digest]; payload bytes stay where they are (ByteBufList(header, data)).
         An entry outside `payload` gets digest 0 and raises BKD_ERR_BOUNDS from the stream's next
         bkd_stream_sync (here, when ``sync_check``)."""
-        import torch
-        n = offsets.numel()
-        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
-        dev = payload.device
-        frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-        digests = torch.empty(n, dtype=torch.int32, device=dev)
-        i64, u32 = torch.int64, _ck._u32_dtypes()
-        with _ck._on_device(payload):
-            st = _ck._stream_ptr(stream, payload)
-            check(lib().bkd_digest_package_batch(
-                self.algo, self.ledgerId, _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
-                _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
-                _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
-                _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
-                _ck._dev_ptr(frames, "frames"), stride, _ck._dev_ptr(digests, "digests"), st))
-            if sync_check:
-                check(lib().bkd_stream_sync(st))
-        return frames, digests
+        return _package_frames("bkd_digest_package_batch", (self.algo, self.ledgerId), self.macCodeLength, (),
+                               entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride, None, stream,
+                               sync_check)
 
     def verify_batch(self, framed, offsets, lengths, first_entry_id: int, skip_entry_check: bool = False,
                      stream=None):
@@ -196,9 +250,10 @@ class DigestManager:
         dev = framed.device
         status = torch.empty(n, dtype=torch.int32, device=dev)
         first_bad = torch.empty(1, dtype=torch.int64, device=dev)
+        first, _keep = self._c_first()
         with _ck._on_device(framed):
-            check(lib().bkd_digest_verify_batch(
-                self.algo, self.ledgerId, first_entry_id, int(skip_entry_check), _ck._dev_ptr(framed, "framed"),
+            check(getattr(lib(), "bkd_digest_verify_batch" + self._c_suffix)(
+                first, self.ledgerId, first_entry_id, int(skip_entry_check), _ck._dev_ptr(framed, "framed"),
                 framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", torch.int64, dev),
                 _ck._dev_ptr(lengths, "lengths", _ck._u32_dtypes(), dev, n), n, _ck._dev_ptr(status, "status"),
                 _ck._dev_ptr(first_bad, "first_bad"), _ck._stream_ptr(stream, framed)))
@@ -292,14 +347,13 @@ class DigestManager:
         """BatchedReadOp.complete over a ByteBufList (BatchedReadOp.java:164-190): `frames` is a
         sequence of host buffers, each one framed entry. Returns (status int32[n], first_bad) with
         first_bad = n when every entry verified, else the verified prefix's length."""
-        views = [_ck._host_view(f) for f in frames]
+        views, ptrs, lens = _ck._host_entries(frames)
         n = len(views)
-        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-        lens = np.array([v.size for v in views], dtype=np.uint32)
         status = np.zeros(n, dtype=np.int32)
         first_bad = ctypes.c_uint64(0)
-        check(lib().bkd_digest_verify_batch_host(
-            self.algo, self.ledgerId, first_entry_id, int(skip_entry_check), ctypes.c_void_p(ptrs.ctypes.data),
+        first, _keep = self._c_first()
+        check(getattr(lib(), f"bkd_digest_verify_batch{self._c_suffix}_host")(
+            first, self.ledgerId, first_entry_id, int(skip_entry_check), ctypes.c_void_p(ptrs.ctypes.data),
             ctypes.c_void_p(lens.ctypes.data), n, ctypes.c_void_p(status.ctypes.data), ctypes.byref(first_bad)))
         del views
         return status, int(first_bad.value)
@@ -307,24 +361,8 @@ class DigestManager:
     def package_batch_host(self, entry_ids, lacs, length_fields, payloads, frame_stride=None):
         """PendingAddOp / LedgerFragmentReplicator packaging of host payloads (DigestManager.java:117-181)
         in one call: returns (headers uint8[n, frame_stride] = [32 B header][digest], digests uint32[n])."""
-        views = [_ck._host_view(p) for p in payloads]
-        n = len(views)
-        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
-        ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
-        lac = np.ascontiguousarray(lacs, dtype=np.int64)
-        lf = np.ascontiguousarray(length_fields, dtype=np.int64)
-        if not (ids.size == lac.size == lf.size == n):
-            raise ValueError("entry_ids, lacs, length_fields and payloads must have one element per entry")
-        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-        lens = np.array([v.size for v in views], dtype=np.uint32)
-        frames = np.zeros((n, stride), dtype=np.uint8)
-        digests = np.zeros(n, dtype=np.uint32)
-        vp = ctypes.c_void_p
-        check(lib().bkd_digest_package_batch_host(
-            self.algo, self.ledgerId, vp(ids.ctypes.data), vp(lac.ctypes.data), vp(lf.ctypes.data),
-            vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
-        del views
-        return frames, digests
+        return _package_frames_host("bkd_digest_package_batch_host", (self.algo, self.ledgerId), self.macCodeLength,
+                                    None, entry_ids, lacs, length_fields, payloads, frame_stride)
 
     def package_batch_segments_host(self, entry_ids, lacs, length_fields, payloads, frame_stride=None):
         """``package_batch_host`` for composite payloads: each payload is a bytes-like object, a sequence
@@ -343,15 +381,13 @@ class DigestManager:
         (status int32[n], first_bad, digests uint32[n])."""
         if any(isinstance(f, np.ndarray) and not f.flags.c_contiguous for f in frames):
             raise TypeError("frames must be contiguous: they are re-framed in place")
-        views = [_ck._host_view(f) for f in frames]
+        views, ptrs, lens = _ck._host_entries(frames)
         if any(not v.flags.writeable for v in views):
             raise TypeError("frames must be writable buffers: they are re-framed in place")
         n = len(views)
         lacs = np.ascontiguousarray(new_lacs, dtype=np.int64)
         if lacs.size != n:
             raise ValueError("new_lacs must have one element per frame")
-        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-        lens = np.array([v.size for v in views], dtype=np.uint32)
         status = np.zeros(n, dtype=np.int32)
         digests = np.zeros(n, dtype=np.uint32)
         first_bad = ctypes.c_uint64(0)
@@ -424,25 +460,9 @@ def package_batch_ledgers(digest_type, ledger_ids, entry_ids, lacs, length_field
                           frame_stride=None, stream=None, sync_check: bool = False):
     """``DigestManager.package_batch`` with ledger_ids[i] (int64[n]) framing entry i: returns
     (frames[n, frame_stride] uint8, digests int32[n])."""
-    import torch
     algo = _algo_of(digest_type)
-    n = offsets.numel()
-    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
-    dev = payload.device
-    frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-    digests = torch.empty(n, dtype=torch.int32, device=dev)
-    i64, u32 = torch.int64, _ck._u32_dtypes()
-    with _ck._on_device(payload):
-        st = _ck._stream_ptr(stream, payload)
-        check(lib().bkd_digest_package_batch_ledgers(
-            algo, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
-            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
-            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
-            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
-            _ck._dev_ptr(frames, "frames"), stride, _ck._dev_ptr(digests, "digests"), st))
-        if sync_check:
-            check(lib().bkd_stream_sync(st))
-    return frames, digests
+    return _package_frames("bkd_digest_package_batch_ledgers", (algo,), _mac_of(algo), (ledger_ids,), entry_ids, lacs,
+                           length_fields, payload, offsets, lengths, frame_stride, None, stream, sync_check)
 
 
 def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry_ids, skip_flags=None):
@@ -450,7 +470,7 @@ def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry
     framed entry; the request arrays are host sequences. A malformed req_first raises
     BKD_ERR_INVALID_ARG before any work. Returns (status int32[n], req_first_bad uint64[nreq])."""
     algo = _algo_of(digest_type)
-    views = [_ck._host_view(f) for f in frames]
+    views, ptrs, lens = _ck._host_entries(frames)
     n = len(views)
     first = np.ascontiguousarray(req_first, dtype=np.uint64)
     if first.size < 1:
@@ -460,8 +480,6 @@ def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry
     eids = np.ascontiguousarray(first_entry_ids, dtype=np.int64)
     flags = np.zeros(nreq, dtype=np.uint32) if skip_flags is None else np.ascontiguousarray(skip_flags, dtype=np.uint32)
     _check_csr_sizes(nreq, lids.size, eids.size, flags.size)
-    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-    lens = np.array([v.size for v in views], dtype=np.uint32)
     status = np.zeros(n, dtype=np.int32)
     first_bad = np.zeros(nreq, dtype=np.uint64)
     vp = ctypes.c_void_p
@@ -476,25 +494,9 @@ def package_batch_ledgers_host(digest_type, ledger_ids, entry_ids, lacs, length_
     """``DigestManager.package_batch_host`` with ledger_ids[i] framing entry i: returns
     (headers uint8[n, frame_stride] = [32 B header][digest], digests uint32[n])."""
     algo = _algo_of(digest_type)
-    views = [_ck._host_view(p) for p in payloads]
-    n = len(views)
-    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
-    lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
-    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
-    lac = np.ascontiguousarray(lacs, dtype=np.int64)
-    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
-    if not (lids.size == ids.size == lac.size == lf.size == n):
-        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
-    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-    lens = np.array([v.size for v in views], dtype=np.uint32)
-    frames = np.zeros((n, stride), dtype=np.uint8)
-    digests = np.zeros(n, dtype=np.uint32)
-    vp = ctypes.c_void_p
-    check(lib().bkd_digest_package_batch_ledgers_host(
-        algo, vp(lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data), vp(lf.ctypes.data), vp(ptrs.ctypes.data),
-        vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
-    del views
-    return frames, digests
+    return _package_frames_host("bkd_digest_package_batch_ledgers_host", (algo,), _mac_of(algo),
+                                np.ascontiguousarray(ledger_ids, dtype=np.int64), entry_ids, lacs, length_fields,
+                                payloads, frame_stride)
 
 
 # ---- composite payloads (a CompositeByteBuf add: DigestManager.java:62-72, 126-181, 380-392) ----
@@ -564,12 +566,7 @@ def _package_segments_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_
     np.cumsum([len(l) for l in leaves], out=seg_first[1:])
     views, ptrs, lens, first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
     stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
-    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
-    lac = np.ascontiguousarray(lacs, dtype=np.int64)
-    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
-    lids = None if ledger_ids is None else np.ascontiguousarray(ledger_ids, dtype=np.int64)
-    if not (ids.size == lac.size == lf.size == n) or (lids is not None and lids.size != n):
-        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
+    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
     frames = np.zeros((n, stride), dtype=np.uint8)
     digests = np.zeros(n, dtype=np.uint32)
     vp = ctypes.c_void_p
@@ -681,19 +678,12 @@ def _package_v2_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields
                      flags, small_threshold):
     if algo is None:
         raise NotImplementedError("DUMMY digests need no device work")
-    views = [_ck._host_view(p) for p in payloads]
+    views, ptrs, lens = _ck._host_entries(payloads)
     n = len(views)
-    ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
-    lac = np.ascontiguousarray(lacs, dtype=np.int64)
-    lf = np.ascontiguousarray(length_fields, dtype=np.int64)
-    lids = None if ledger_ids is None else np.ascontiguousarray(ledger_ids, dtype=np.int64)
-    if not (ids.size == lac.size == lf.size == n) or (lids is not None and lids.size != n):
-        raise ValueError("ledger_ids, entry_ids, lacs, length_fields and payloads must have one element per entry")
+    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
     if not isinstance(master_key, (bytes, bytearray, memoryview)):
         master_key = np.ascontiguousarray(master_key, dtype=np.uint8)
     keys, stride = _master_keys(master_key, n, key_stride)
-    ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-    lens = np.array([v.size for v in views], dtype=np.uint32)
     offs, total = request_offsets_v2(request_sizes_v2(algo, lens, small_threshold))
     buf = np.zeros(int(total) if n else 0, dtype=np.uint8)
     rptr = (buf.ctypes.data + offs).astype(np.uint64)
@@ -795,7 +785,13 @@ class MacDigestManager(DigestManager):
     def isInt32Digest(self) -> bool:
         return False
 
-    # ---- batches ----
+    # ---- batches: verify_batch and verify_batch_host are the base class's, through these two ----
+    _c_suffix = "_mac"
+
+    def _c_first(self):
+        ks, kp = _ck._key_ptr(self.key_state)
+        return kp, ks
+
     def package_batch(self, entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride=None,
                       stream=None, sync_check: bool = False, out_frames=None):
         """As ``DigestManager.package_batch`` with frames of [32 B header][20 B MAC] (``out_frames``: a
@@ -804,83 +800,22 @@ class MacDigestManager(DigestManager):
         out of range or longer than MAC_MAX_ENTRY is not read: zero MAC, BKD_ERR_BOUNDS from the stream's
         next sync (here, when ``sync_check``)."""
         import torch
-        n = offsets.numel()
-        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
-        dev = payload.device
-        if out_frames is None:
-            out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-        elif out_frames.dim() != 2 or out_frames.shape[0] < n or out_frames.shape[1] != stride:
-            raise ValueError("out_frames must be a [n, frame_stride] tensor")
-        frames = out_frames
-        i64, u32 = torch.int64, _ck._u32_dtypes()
-        ks, kp = _ck._key_ptr(self.key_state)
+        first, _keep = self._c_first()
+        frames, _ = _package_frames("bkd_digest_package_batch_mac", (first, self.ledgerId), self.macCodeLength, (),
+                                    entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride, out_frames,
+                                    stream, sync_check, with_digests=False)
         with _ck._on_device(payload):
-            st = _ck._stream_ptr(stream, payload)
-            check(lib().bkd_digest_package_batch_mac(
-                kp, self.ledgerId, _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
-                _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
-                _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
-                _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
-                _ck._dev_ptr(frames, "frames", torch.uint8, dev), stride, st))
-            if sync_check:
-                check(lib().bkd_stream_sync(st))
             with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
                 macs = frames[:, METADATA_LENGTH:METADATA_LENGTH + self.macCodeLength].contiguous()
         return frames, macs
 
-    def verify_batch(self, framed, offsets, lengths, first_entry_id: int, skip_entry_check: bool = False,
-                     stream=None):
-        """As ``DigestManager.verify_batch``: (status int32[n], first_bad int64[1])."""
-        import torch
-        n = offsets.numel()
-        dev = framed.device
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        first_bad = torch.empty(1, dtype=torch.int64, device=dev)
-        ks, kp = _ck._key_ptr(self.key_state)
-        with _ck._on_device(framed):
-            check(lib().bkd_digest_verify_batch_mac(
-                kp, self.ledgerId, first_entry_id, int(skip_entry_check), _ck._dev_ptr(framed, "framed"),
-                framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", torch.int64, dev),
-                _ck._dev_ptr(lengths, "lengths", _ck._u32_dtypes(), dev, n), n, _ck._dev_ptr(status, "status"),
-                _ck._dev_ptr(first_bad, "first_bad"), _ck._stream_ptr(stream, framed)))
-        return status, first_bad
-
-    def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
-        """As ``DigestManager.verify_batch_host``: (status int32[n], first_bad)."""
-        views = [_ck._host_view(f) for f in frames]
-        n = len(views)
-        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-        lens = np.array([v.size for v in views], dtype=np.uint32)
-        status = np.zeros(n, dtype=np.int32)
-        first_bad = ctypes.c_uint64(0)
-        ks, kp = _ck._key_ptr(self.key_state)
-        vp = ctypes.c_void_p
-        check(lib().bkd_digest_verify_batch_mac_host(
-            kp, self.ledgerId, first_entry_id, int(skip_entry_check), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n,
-            vp(status.ctypes.data), ctypes.byref(first_bad)))
-        del views
-        return status, int(first_bad.value)
-
     def package_batch_host(self, entry_ids, lacs, length_fields, payloads, frame_stride=None):
         """As ``DigestManager.package_batch_host``: (headers uint8[n, frame_stride] = [32 B header]
         [20 B MAC], macs uint8[n, 20])."""
-        views = [_ck._host_view(p) for p in payloads]
-        n = len(views)
-        stride = frame_stride or (METADATA_LENGTH + self.macCodeLength)
-        ids = np.ascontiguousarray(entry_ids, dtype=np.int64)
-        lac = np.ascontiguousarray(lacs, dtype=np.int64)
-        lf = np.ascontiguousarray(length_fields, dtype=np.int64)
-        if not (ids.size == lac.size == lf.size == n):
-            raise ValueError("entry_ids, lacs, length_fields and payloads must have one element per entry")
-        ptrs = np.array([v.ctypes.data if v.size else 0 for v in views], dtype=np.uint64)
-        lens = np.array([v.size for v in views], dtype=np.uint32)
-        frames = np.zeros((n, stride), dtype=np.uint8)
-        ks, kp = _ck._key_ptr(self.key_state)
-        vp = ctypes.c_void_p
-        check(lib().bkd_digest_package_batch_mac_host(
-            kp, self.ledgerId, vp(ids.ctypes.data), vp(lac.ctypes.data), vp(lf.ctypes.data), vp(ptrs.ctypes.data),
-            vp(lens.ctypes.data), n, vp(frames.ctypes.data), stride))
-        del views
+        first, _keep = self._c_first()
+        frames, _ = _package_frames_host("bkd_digest_package_batch_mac_host", (first, self.ledgerId),
+                                         self.macCodeLength, None, entry_ids, lacs, length_fields, payloads,
+                                         frame_stride, with_digests=False)
         return frames, frames[:, METADATA_LENGTH:METADATA_LENGTH + self.macCodeLength].copy()
 
     def _no_batch(self, *a, **k):
