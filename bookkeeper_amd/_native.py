@@ -108,6 +108,13 @@ PROTOTYPES = {
     "bkd_mac_batch_host": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "bkd_digest_package_batch_mac_host": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64]),
     "bkd_digest_verify_batch_mac_host": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _u64, _vp, _vp]),
+    "bkd_digest_verify_requests_mac": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
+                                              _vp, _vp]),
+    "bkd_digest_package_batch_ledgers_mac": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                                    _u64, _vp]),
+    "bkd_digest_verify_requests_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "bkd_digest_package_batch_ledgers_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp,
+                                                         _u64]),
     "bkd_entrylog_index": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_verify": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),

@@ -1632,15 +1632,18 @@ int mac_raw(DeviceState& ds, hipStream_t st, const uint32_t* key_state, const vo
     return BKD_OK;
 }
 
-int mac_package(DeviceState& ds, hipStream_t st, const uint32_t* key_state, int64_t ledger_id, const int64_t* d_entry_ids,
-                const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload, uint64_t size,
-                const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, void* d_frames, uint64_t stride) {
+// The package kernel over `who` (bkd::MacOneLedger: one ledger's key and id; bkd::MacLedgers: a key table
+// and a ledger id per entry).
+template <class Who>
+int mac_package(DeviceState& ds, hipStream_t st, const Who& who, const int64_t* d_entry_ids, const int64_t* d_lacs,
+                const int64_t* d_length_fields, const void* d_payload, uint64_t size, const uint64_t* d_offsets,
+                const uint32_t* d_lengths, uint64_t n, void* d_frames, uint64_t stride) {
     uint32_t* err = nullptr;
     const int rc = bounds_flag(ds, st, &err);
     if (rc) return rc;
-    hipLaunchKernelGGL(bkd::mac_package_kernel, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, mac_key(key_state),
-                       ledger_id, d_entry_ids, d_lacs, d_length_fields, (const uint8_t*)d_payload, size, d_offsets,
-                       d_lengths, n, (uint8_t*)d_frames, stride, err);
+    hipLaunchKernelGGL(bkd::mac_package_kernel<Who>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who, d_entry_ids,
+                       d_lacs, d_length_fields, (const uint8_t*)d_payload, size, d_offsets, d_lengths, n,
+                       (uint8_t*)d_frames, stride, err);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
 }
@@ -1661,9 +1664,82 @@ int mac_verify(DeviceState& ds, hipStream_t st, const uint32_t* key_state, int64
     std::lock_guard<std::recursive_mutex> lk(sc.mu);  // the two launches as one sequence
     hipLaunchKernelGGL(bkd::reframe_first_bad_kernel, dim3(1), dim3(1), 0, st, d_first_bad, n);
     BKD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkd::mac_verify_kernel, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, mac_key(key_state),
-                       ledger_id, first_entry_id, id_checks, (const uint8_t*)d_framed, size, d_offsets, d_lengths, n,
-                       d_status, (unsigned long long*)d_first_bad, err);
+    const bkd::MacOneRead who{mac_key(key_state), ledger_id, first_entry_id, id_checks, (unsigned long long*)d_first_bad};
+    hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacOneRead>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                       (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
+// A key table in device memory and who indexes it: per request (verify) or per entry (package).
+struct MacKeys {
+    const uint32_t* states;
+    uint64_t nkeys;
+    const uint32_t* index;
+};
+
+// A host key table on the current device for the length of one host-resident call: one allocation and one
+// blocking copy, so every staged segment of the call, on either slot's stream, finds it there.
+struct DeviceTable {
+    uint32_t* d = nullptr;
+    int upload(const uint32_t* h_key_states, uint64_t nkeys) {
+        if (d || nkeys == 0) return BKD_OK;
+        const hipError_t e = hipMalloc((void**)&d, nkeys * 10u * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return fail(BKD_ERR_NOMEM, std::string("key table: ") + hipGetErrorString(e));
+        }
+        BKD_HIP(hipMemcpy(d, h_key_states, nkeys * 10u * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return BKD_OK;
+    }
+    ~DeviceTable() {
+        if (d) (void)hipFree(d);
+    }
+};
+
+// Read requests of MAC ledgers (bkd_digest_verify_requests_mac; rq as verify_framed takes it, keys.index
+// per request): the CSR expanded into the stream's verify scratch and checked and the prefixes initialised
+// by request_expand_kernel, then the verify kernel over bkd::MacRequests.
+int mac_verify_requests(DeviceState& ds, hipStream_t st, const MacKeys& keys, const void* d_framed, uint64_t size,
+                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, int32_t* d_status,
+                        const Requests& rq) {
+    if (n == 0) {
+        if (rq.nreq) BKD_HIP(hipMemsetAsync(rq.first_bad, 0, rq.nreq * sizeof(uint64_t), st));
+        return BKD_OK;
+    }
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    Carver cv;
+    const size_t o_xlid = cv.take(n * 8), o_xeid = cv.take(n * 8), o_req = cv.take(n * 4);
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // the scratch and the two launches as one sequence
+    uint8_t* sb = nullptr;
+    const hipError_t e = sc.get(1, cv.used, st, &sb);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("verify scratch: ") + hipGetErrorString(e));
+    int64_t *xlid = Carver::at<int64_t>(sb, o_xlid), *xeid = Carver::at<int64_t>(sb, o_xeid);
+    uint32_t* req_of = Carver::at<uint32_t>(sb, o_req);
+    const unsigned xblocks = (unsigned)std::min<uint64_t>((std::max(n, rq.nreq) + 255) / 256, 8u * (uint64_t)ds.cus);
+    hipLaunchKernelGGL(bkd::request_expand_kernel, dim3(xblocks), dim3(256), 0, st, rq.first, rq.nreq, n, rq.ledger_ids,
+                       rq.first_entry_ids, rq.flags, xlid, xeid, req_of, (unsigned long long*)rq.first_bad, err);
+    BKD_HIP(hipGetLastError());
+    const bkd::MacRequests who{keys.states, keys.nkeys, keys.index,
+                               bkd::RequestIds{xlid, xeid, req_of, rq.first, (unsigned long long*)rq.first_bad}};
+    hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacRequests>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                       (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
+// The verify kernel over one staged segment of the host form: who holds the segment's expectations.
+int mac_verify_expected(DeviceState& ds, hipStream_t st, const bkd::MacExpected& who, const void* d_framed,
+                        uint64_t size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                        int32_t* d_status) {
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacExpected>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                       (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
 }
@@ -2488,8 +2564,8 @@ int bkd_digest_package_batch_mac(const uint32_t* key_state, int64_t ledger_id, c
     if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
     Call call(stream);
     if (call.rc) return call.rc;
-    return mac_package(*call.ds, call.st, key_state, ledger_id, d_entry_ids, d_lacs, d_length_fields, d_payload,
-                       payload_size, d_offsets, d_lengths, n, d_frames, frame_stride);
+    return mac_package(*call.ds, call.st, bkd::MacOneLedger{mac_key(key_state), ledger_id}, d_entry_ids, d_lacs,
+                       d_length_fields, d_payload, payload_size, d_offsets, d_lengths, n, d_frames, frame_stride);
 }
 
 int bkd_digest_verify_batch_mac(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id,
@@ -2558,8 +2634,8 @@ int bkd_digest_package_batch_mac_host(const uint32_t* key_state, int64_t ledger_
     // the device writes packed 52-byte frames and no digest words; the host puts each frame at its stride
     auto launch = [=](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t*, uint64_t cnt,
                       uint64_t bytes, uint64_t stride) {
-        return mac_package(ds, hs.st[s], key_state, ledger_id, d_ids, d_ids + cnt, d_ids + 2 * cnt, hs.d_buf[s], bytes,
-                           hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
+        return mac_package(ds, hs.st[s], bkd::MacOneLedger{mac_key(key_state), ledger_id}, d_ids, d_ids + cnt,
+                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
     };
     return package_host_staged(nullptr, h_entry_ids, h_lacs, h_length_fields, entry_buffers(h_payloads, h_lengths),
                                h_lengths, n, launch, hl, false, host_frames(hl, hl, h_frames, frame_stride, nullptr));
@@ -2588,6 +2664,180 @@ int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t ledger_i
                               bytes, hs.d_off[s], hs.d_len[s], cnt, reinterpret_cast<int32_t*>(hs.d_res[s]), hs.d_fb[s]);
         },
         h_frames, h_lengths, n, h_status, h_first_bad);
+}
+
+int bkd_digest_verify_requests_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_req_keys,
+                                   const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                                   const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first, uint64_t nreq,
+                                   const int64_t* d_req_ledger_ids, const int64_t* d_req_first_entry_ids,
+                                   const uint32_t* d_req_flags, int32_t* d_status, uint64_t* d_req_first_bad,
+                                   void* stream) {
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if (!d_req_keys || !d_req_first || !d_req_ledger_ids || !d_req_first_entry_ids || !d_req_flags || !d_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    if (nkeys && !d_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
+    if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    const Requests rq{nreq, d_req_first, d_req_ledger_ids, d_req_first_entry_ids, d_req_flags, d_req_first_bad};
+    return mac_verify_requests(*call.ds, call.st, MacKeys{d_key_states, nkeys, d_req_keys}, d_framed, framed_size,
+                               d_offsets, d_lengths, n, d_status, rq);
+}
+
+int bkd_digest_package_batch_ledgers_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                         const int64_t* d_ledger_ids, const int64_t* d_entry_ids, const int64_t* d_lacs,
+                                         const int64_t* d_length_fields, const void* d_payload, uint64_t payload_size,
+                                         const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                         void* d_frames, uint64_t frame_stride, void* stream) {
+    if (n == 0) return BKD_OK;
+    if (!d_key_of || !d_ledger_ids || !d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths ||
+        !d_frames)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !d_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (int rc = check_frame_stride(bkd::host::kMacFrameHead, frame_stride, false)) return rc;
+    if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return mac_package(*call.ds, call.st, bkd::MacLedgers{d_key_states, nkeys, d_key_of, d_ledger_ids}, d_entry_ids,
+                       d_lacs, d_length_fields, d_payload, payload_size, d_offsets, d_lengths, n, d_frames, frame_stride);
+}
+
+int bkd_digest_verify_requests_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_req_keys,
+                                        const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                                        const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
+                                        const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags,
+                                        int32_t* h_status, uint64_t* h_req_first_bad) {
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if (!h_req_keys || !h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags || !h_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    // the key indices and the CSR, before any work: rows of the table; starts at 0, never decreases, ends at n
+    for (uint64_t r = 0; r < nreq; ++r)
+        if (h_req_keys[r] >= nkeys)
+            return fail(BKD_ERR_INVALID_ARG, "request " + std::to_string(r) + " names a key outside the table");
+    if (h_req_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "req_first[0] is not 0");
+    for (uint64_t r = 0; r < nreq; ++r)
+        if (h_req_first[r + 1] < h_req_first[r])
+            return fail(BKD_ERR_INVALID_ARG, "req_first decreases at request " + std::to_string(r));
+    if (h_req_first[nreq] != n) return fail(BKD_ERR_INVALID_ARG, "req_first[nreq] is not n");
+    if (n && (!h_frames || !h_lengths || !h_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
+    for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
+    if (n == 0) return BKD_OK;
+    const int route = mac_host_route(h_lengths, n);
+    if (route < 0) return route;
+    // the requests as per-entry expectations: what the CPU route checks frame by frame and what the GPU
+    // route stages beside the frames, with each entry's key row
+    std::vector<int64_t> xlid(n), xeid(n);
+    std::vector<uint32_t> req_of(n);
+    for (uint64_t r = 0; r < nreq; ++r)
+        for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i) {
+            xlid[i] = h_req_ledger_ids[r];
+            xeid[i] = (int64_t)((uint64_t)h_req_first_entry_ids[r] + (i - h_req_first[r]));
+            req_of[i] = (uint32_t)r | ((h_req_flags[r] & 1u) ? bkd::host::kSkipEntryId : 0u);
+        }
+    // the statuses come back to the host on either route, and a request's verified prefix is its first
+    // non-zero status: a request that straddles two staged segments gets the minimum over both parts
+    auto prefixes = [&] {
+        for (uint64_t r = 0; r < nreq; ++r)
+            for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i)
+                if (h_status[i] != 0) {
+                    h_req_first_bad[r] = i - h_req_first[r];
+                    break;
+                }
+    };
+    if (route == 1) {
+        bkd::host::mac_verify_frames_expected(h_key_states, h_req_keys, xlid.data(), xeid.data(), req_of.data(),
+                                              (const uint8_t* const*)h_frames, h_lengths, n, h_status);
+        prefixes();
+        return BKD_OK;
+    }
+    StagedCall call(&HostStage::init_requests);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    DeviceTable keys;  // uploaded once, before any segment is enqueued
+    if (int rc = keys.upload(h_key_states, nkeys)) return rc;
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        const hipStream_t st = hs.st[s];
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        // [ledger ids][entry ids][flag words] in the requests buffer, the key rows in the seeds buffer
+        const size_t o_eid = cnt * 8, o_flag = cnt * 16;
+        memcpy(hs.h_rq[s], xlid.data() + i0, cnt * 8);
+        memcpy(hs.h_rq[s] + o_eid, xeid.data() + i0, cnt * 8);
+        uint32_t* flag = reinterpret_cast<uint32_t*>(hs.h_rq[s] + o_flag);
+        for (uint64_t j = 0; j < cnt; ++j) {
+            flag[j] = req_of[i0 + j] & bkd::host::kSkipEntryId;
+            hs.h_seed[s][j] = h_req_keys[req_of[i0 + j] & ~bkd::host::kSkipEntryId];
+        }
+        BKD_HIP(hipMemcpyAsync(hs.d_rq[s], hs.h_rq[s], cnt * 20, hipMemcpyHostToDevice, st));
+        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, st));
+        const uint8_t* d = hs.d_rq[s];
+        const bkd::MacExpected who{keys.d, nkeys, hs.d_seed[s], reinterpret_cast<const int64_t*>(d),
+                                   reinterpret_cast<const int64_t*>(d + o_eid),
+                                   reinterpret_cast<const uint32_t*>(d + o_flag)};
+        r = mac_verify_expected(*call.ds, st, who, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
+                                reinterpret_cast<int32_t*>(hs.d_res[s]));
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
+        return BKD_OK;
+    };
+    const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
+    if (rc == BKD_OK) prefixes();
+    return rc;
+}
+
+int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
+                                              const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                                              const int64_t* h_lacs, const int64_t* h_length_fields,
+                                              const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
+                                              void* h_frames, uint64_t frame_stride) {
+    if (n == 0) return BKD_OK;
+    if (!h_key_of || !h_ledger_ids || !h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths ||
+        !h_frames)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    constexpr uint64_t hl = bkd::host::kMacFrameHead;
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    for (uint64_t i = 0; i < n; ++i)  // before any work, so no frame is written
+        if (h_key_of[i] >= nkeys)
+            return fail(BKD_ERR_INVALID_ARG, "entry " + std::to_string(i) + " names a key outside the table");
+    if (int rc = check_host_entries("entry", h_payloads, h_lengths, n)) return rc;
+    const int route = mac_host_route(h_lengths, n);
+    if (route < 0) return route;
+    if (route == 1) {
+        bkd::host::mac_package_frames_ledgers(h_key_states, h_key_of, h_ledger_ids, h_entry_ids, h_lacs,
+                                              h_length_fields, (const uint8_t* const*)h_payloads, h_lengths, n,
+                                              (uint8_t*)h_frames, frame_stride);
+        return BKD_OK;
+    }
+    DeviceTable keys;  // uploaded once, by the first segment (the staged call has entered the device by then)
+    // each segment's key rows travel in the seeds buffer, beside the payloads
+    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        int r = keys.upload(h_key_states, nkeys);
+        if (r) return r;
+        r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        memcpy(hs.h_seed[s], h_key_of + i0, cnt * 4);
+        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+        return BKD_OK;
+    };
+    // the device writes packed 52-byte frames and no digest words; the host puts each frame at its stride
+    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
+                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
+        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
+                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
+    };
+    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch, hl, false,
+                               host_frames(hl, hl, h_frames, frame_stride, nullptr));
 }
 
 int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,

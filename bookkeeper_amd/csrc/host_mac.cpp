@@ -119,23 +119,34 @@ void mac_list(const uint32_t* key_state, const uint8_t* const* ptrs, const uint3
     each_entry(n, lens, [&](uint64_t i) { mac_one(key_state, nullptr, 0, ptrs[i], lens[i], out + i * kMacLen); });
 }
 
+// DigestManager.verifyDigest for one MAC frame (DigestManager.java:226-283): too short, digest, ledger
+// id, entry id (unless skipped), in that order.
+static int32_t mac_verify_one(const uint32_t* key_state, const uint8_t* f, uint32_t l, int64_t ledger_id, int64_t entry_id,
+                              bool skip_entry_id) {
+    if (l < kMacFrameHead) return 1;
+    uint8_t mac[kMacLen];
+    mac_one(key_state, f, 32, f + kMacFrameHead, l - kMacFrameHead, mac);
+    const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
+    const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
+    if (memcmp(mac, f + 32, kMacLen) != 0) return 2;
+    if (lid != ledger_id) return 3;
+    return (!skip_entry_id && eid != entry_id) ? 4 : 0;
+}
+
+// The header and the MAC of one entry into f (DigestManager.java:146-155, 172-178): 52 bytes.
+static void mac_package_one(const uint32_t* key_state, int64_t ledger_id, int64_t entry_id, int64_t lac, int64_t length_field,
+                            const uint8_t* payload, uint32_t len, uint8_t* f) {
+    put_be64(f, (uint64_t)ledger_id);
+    put_be64(f + 8, (uint64_t)entry_id);
+    put_be64(f + 16, (uint64_t)lac);
+    put_be64(f + 24, (uint64_t)length_field);
+    mac_one(key_state, f, 32, payload, len, f + 32);
+}
+
 uint64_t mac_verify_frames(const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id, int id_checks,
                            const uint8_t* const* frames, const uint32_t* lens, uint64_t n, int32_t* status) {
     each_entry(n, lens, [&](uint64_t i) {
-        const uint8_t* f = frames[i];
-        const uint32_t l = lens[i];
-        if (l < kMacFrameHead) {
-            status[i] = 1;
-            return;
-        }
-        uint8_t mac[kMacLen];
-        mac_one(key_state, f, 32, f + kMacFrameHead, l - kMacFrameHead, mac);
-        const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
-        const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
-        if (memcmp(mac, f + 32, kMacLen) != 0) status[i] = 2;
-        else if (lid != ledger_id) status[i] = 3;
-        else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) status[i] = 4;
-        else status[i] = 0;
+        status[i] = mac_verify_one(key_state, frames[i], lens[i], ledger_id, first_entry_id + (int64_t)i, id_checks != 0);
     });
     for (uint64_t i = 0; i < n; ++i)
         if (status[i] != 0) return i;
@@ -146,12 +157,27 @@ void mac_package_frames(const uint32_t* key_state, int64_t ledger_id, const int6
                         const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
                         uint64_t n, uint8_t* frames, uint64_t stride) {
     each_entry(n, lens, [&](uint64_t i) {
-        uint8_t* f = frames + i * stride;
-        put_be64(f, (uint64_t)ledger_id);
-        put_be64(f + 8, (uint64_t)entry_ids[i]);
-        put_be64(f + 16, (uint64_t)lacs[i]);
-        put_be64(f + 24, (uint64_t)length_fields[i]);
-        mac_one(key_state, f, 32, payloads[i], lens[i], f + 32);
+        mac_package_one(key_state, ledger_id, entry_ids[i], lacs[i], length_fields[i], payloads[i], lens[i],
+                        frames + i * stride);
+    });
+}
+
+void mac_verify_frames_expected(const uint32_t* key_states, const uint32_t* req_keys, const int64_t* ledger_ids,
+                                const int64_t* entry_ids, const uint32_t* req_of, const uint8_t* const* frames,
+                                const uint32_t* lens, uint64_t n, int32_t* status) {
+    each_entry(n, lens, [&](uint64_t i) {
+        const uint32_t* key = key_states + (uint64_t)req_keys[req_of[i] & ~kSkipEntryId] * 10u;
+        status[i] = mac_verify_one(key, frames[i], lens[i], ledger_ids[i], entry_ids[i], (req_of[i] & kSkipEntryId) != 0);
+    });
+}
+
+void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_of, const int64_t* ledger_ids,
+                                const int64_t* entry_ids, const int64_t* lacs, const int64_t* length_fields,
+                                const uint8_t* const* payloads, const uint32_t* lens, uint64_t n, uint8_t* frames,
+                                uint64_t stride) {
+    each_entry(n, lens, [&](uint64_t i) {
+        mac_package_one(key_states + (uint64_t)key_of[i] * 10u, ledger_ids[i], entry_ids[i], lacs[i], length_fields[i],
+                        payloads[i], lens[i], frames + i * stride);
     });
 }
 

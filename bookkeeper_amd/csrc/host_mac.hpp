@@ -33,6 +33,18 @@ uint64_t mac_verify_frames(const uint32_t* key_state, int64_t ledger_id, int64_t
 void mac_package_frames(const uint32_t* key_state, int64_t ledger_id, const int64_t* entry_ids, const int64_t* lacs,
                         const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
                         uint64_t n, uint8_t* frames, uint64_t stride);
+// Batches that span ledgers (bkd_digest_verify_requests_mac_host, bkd_digest_package_batch_ledgers_mac_host):
+// key_states is a table of ten-word rows. Verify: frame i against ledger_ids[i] and entry_ids[i], keyed
+// with row req_keys[r] for its request r = req_of[i] & ~kSkipEntryId (host_batch.hpp; the bit skips the
+// entry-id check), as verify_frames_expected. Package: entry i framed for ledger_ids[i] and keyed with row
+// key_of[i], as package_frames_ledgers. Every index is the caller's to check against the table's rows.
+void mac_verify_frames_expected(const uint32_t* key_states, const uint32_t* req_keys, const int64_t* ledger_ids,
+                                const int64_t* entry_ids, const uint32_t* req_of, const uint8_t* const* frames,
+                                const uint32_t* lens, uint64_t n, int32_t* status);
+void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_of, const int64_t* ledger_ids,
+                                const int64_t* entry_ids, const int64_t* lacs, const int64_t* length_fields,
+                                const uint8_t* const* payloads, const uint32_t* lens, uint64_t n, uint8_t* frames,
+                                uint64_t stride);
 
 }  // namespace host
 }  // namespace bkd

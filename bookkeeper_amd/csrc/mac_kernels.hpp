@@ -12,11 +12,19 @@
 // dwords that lie outside the entry never reach the hash.
 //
 // Ragged batches: lanes whose entry is finished idle until the wave's longest entry ends.
+//
+// Keys and ids. The package and verify kernels are templates over a policy that supplies, per entry, the
+// key state and the ledger id (package) or the expected ids and the verified-prefix word (verify), as
+// OneRead / RequestIds do for the CRC verify kernels: MacOneLedger / MacOneRead are one ledger's key as
+// a kernel argument (SGPRs); MacLedgers / MacRequests index a table of key states in device memory, so a
+// batch spans ledgers with a key each. A table row's inner words are loaded into the hash state before
+// the first block and its outer words only after the inner hash, so neither is held across the rounds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/bkdigest.h"
+#include "crc_kernels.hpp"
 #include "mac_sha1.hpp"
 
 namespace bkd {
@@ -26,6 +34,20 @@ constexpr int kMacBlock = 256;
 // The ledger's key state (bkd_mac_key_init), a kernel argument: [0..4] inner, [5..9] outer.
 struct MacKey {
     uint32_t s[10];
+    __device__ __forceinline__ const uint32_t* inner() const { return s; }
+    __device__ __forceinline__ const uint32_t* outer() const { return s + 5; }
+};
+
+// Row k of a key table (nkeys x 10 words in device memory, each row what bkd_mac_key_init writes), or no
+// row when k >= nkeys: such an entry is unreadable, and no word outside the table is ever loaded. A lane
+// holds the index (one VGPR; the table is the wave's, in SGPRs) and forms the address where it loads.
+struct MacKeyRow {
+    const uint32_t* __restrict__ states;
+    uint64_t nkeys;
+    uint32_t k;
+    __device__ __forceinline__ bool valid() const { return k < nkeys; }
+    __device__ __forceinline__ const uint32_t* inner() const { return states + (uint64_t)k * 10u; }
+    __device__ __forceinline__ const uint32_t* outer() const { return inner() + 5; }
 };
 
 // An entry's bytes as a stream of aligned dwords: dword k is a[k], valid (it holds a byte of the
@@ -58,16 +80,17 @@ struct MacStream {
 };
 
 // mac[5] = HMAC over pre[0..8) (PREFIX: the 32-byte frame header as big-endian words) followed by the
-// len bytes of the stream that start at its dword k0 (byte `shift` of it).
-template <bool PREFIX>
-__device__ __forceinline__ void mac_entry(const MacKey& key, const uint32_t (&pre)[8], const MacStream& in,
+// len bytes of the stream that start at its dword k0 (byte `shift` of it). key: MacKey or MacKeyRow; the
+// outer words are read only after the inner hash.
+template <bool PREFIX, class Key>
+__device__ __forceinline__ void mac_entry(const Key& key, const uint32_t (&pre)[8], const MacStream& in,
                                           uint32_t k0, uint32_t len, uint32_t (&mac)[5]) {
     const uint64_t m = (uint64_t)len + (PREFIX ? 32u : 0u);
     const uint64_t padded = sha1::padded_bytes(m);
     const uint64_t bits = sha1::hmac_inner_bits(m);
     uint32_t h[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) h[k] = key.s[k];
+    for (int k = 0; k < 5; ++k) h[k] = key.inner()[k];
     uint64_t pos = 0;
     uint32_t edge;  // the dword the next block's first word starts in
     {
@@ -112,7 +135,7 @@ __device__ __forceinline__ void mac_entry(const MacKey& key, const uint32_t (&pr
             pos += 64u;
         }
     }
-    sha1::hmac_outer(key.s + 5, h, mac);
+    sha1::hmac_outer(key.outer(), h, mac);
 }
 
 // In range and under the cap: the only entries that are read.
@@ -157,11 +180,48 @@ __global__ void __launch_bounds__(kMacBlock) mac_batch_kernel(MacKey key, const 
     store_be_words(out + i * 20u, mac);
 }
 
+// ---- who keys and frames entry i of a package call ------------------------------------------------
+//   const auto x = who.entry(i);
+//   x.keyed()       the entry has a key (a table index inside the table)
+//   x.key()         MacKey or MacKeyRow
+//   x.ledger_id()   the ledger id its header carries
+
+// One ledger (bkd_digest_package_batch_mac): its key state and id as kernel arguments.
+struct MacOneLedger {
+    MacKey k;
+    int64_t lid;
+    __device__ __forceinline__ const MacOneLedger& entry(uint64_t) const { return *this; }
+    __device__ __forceinline__ bool keyed() const { return true; }
+    __device__ __forceinline__ const MacKey& key() const { return k; }
+    __device__ __forceinline__ int64_t ledger_id() const { return lid; }
+};
+
+// A ledger per entry (bkd_digest_package_batch_ledgers_mac): entry i is framed for ledger_ids[i] and
+// keyed with row key_of[i] of the table.
+struct MacLedgers {
+    const uint32_t* __restrict__ key_states;
+    uint64_t nkeys;
+    const uint32_t* __restrict__ key_of;
+    const int64_t* __restrict__ ledger_ids;
+    struct Entry {
+        MacKeyRow k;
+        int64_t lid;
+        __device__ __forceinline__ bool keyed() const { return k.valid(); }
+        __device__ __forceinline__ const MacKeyRow& key() const { return k; }
+        __device__ __forceinline__ int64_t ledger_id() const { return lid; }
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i) const {
+        return Entry{MacKeyRow{key_states, nkeys, key_of[i]}, ledger_ids[i]};
+    }
+};
+
 // frames + i * stride = [ledger id, entry_ids[i], lacs[i], length_fields[i] as BE longs][20 B mac]
-// (DigestManager.java:146-155, 172-178); no other byte of the stride is written. An unreadable payload:
-// the header is written, the MAC bytes are zero, err is raised.
+// (DigestManager.java:146-155, 172-178); no other byte of the stride is written. An unreadable payload
+// (out of range, over the cap, or without a key): the header is written, the MAC bytes are zero, err is
+// raised.
+template <class Who>
 __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
-    MacKey key, int64_t ledger_id, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
+    Who who, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
     const int64_t* __restrict__ length_fields, const uint8_t* __restrict__ payload, uint64_t size,
     const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n,
     uint8_t* __restrict__ frames, uint64_t stride, uint32_t* __restrict__ err) {
@@ -169,7 +229,9 @@ __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
     if (i >= n) return;
     const uint64_t o = offsets[i];
     const uint32_t l = lengths[i];
-    const uint64_t f4[4] = {(uint64_t)ledger_id, (uint64_t)entry_ids[i], (uint64_t)lacs[i], (uint64_t)length_fields[i]};
+    const auto x = who.entry(i);
+    const uint64_t f4[4] = {(uint64_t)x.ledger_id(), (uint64_t)entry_ids[i], (uint64_t)lacs[i],
+                            (uint64_t)length_fields[i]};
     uint32_t hdr[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -177,9 +239,9 @@ __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
         hdr[2 * k + 1] = (uint32_t)f4[k];
     }
     uint32_t mac[5] = {0u, 0u, 0u, 0u, 0u};
-    if (mac_readable(o, l, size)) {
+    if (x.keyed() && mac_readable(o, l, size)) {
         const MacStream in(payload + o, l);
-        mac_entry<true>(key, hdr, in, 0u, l, mac);
+        mac_entry<true>(x.key(), hdr, in, 0u, l, mac);
     } else {
         atomicOr(err, 1u);
     }
@@ -188,20 +250,108 @@ __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
     store_be_words(f + 32, mac);
 }
 
+// ---- who keys frame i of a verify call and what it must carry ---------------------------------------
+//   const auto x = who.entry(i);
+//   x.keyed(), x.key()    as above
+//   x.id_status(hw, i)    0, 3 (ledger id) or 4 (entry id) from the header's first four words (values)
+//   x.failed(i)           entry i failed: lowers the verified-prefix word it belongs to
+
+// One read (bkd_digest_verify_batch_mac): one key, one ledger id, entry ids first_entry_id + i (id_checks
+// 0 only), one verified-prefix word, initialised to n by an earlier launch.
+struct MacOneRead {
+    MacKey k;
+    int64_t ledger_id, first_entry_id;
+    int id_checks;
+    unsigned long long* first_bad;
+    __device__ __forceinline__ const MacOneRead& entry(uint64_t) const { return *this; }
+    __device__ __forceinline__ bool keyed() const { return true; }
+    __device__ __forceinline__ const MacKey& key() const { return k; }
+    __device__ __forceinline__ int32_t id_status(const uint32_t* hw, uint64_t i) const {
+        const int64_t lid = (int64_t)(((uint64_t)hw[0] << 32) | hw[1]);
+        const int64_t eid = (int64_t)(((uint64_t)hw[2] << 32) | hw[3]);
+        if (lid != ledger_id) return 3;
+        if (id_checks == 0 && eid != first_entry_id + (int64_t)i) return 4;
+        return 0;
+    }
+    __device__ __forceinline__ void failed(uint64_t i) const { atomicMin(first_bad, (unsigned long long)i); }
+};
+
+// Read requests (bkd_digest_verify_requests_mac): the per-entry expectations request_expand_kernel wrote
+// (RequestIds, crc_kernels.hpp) and row req_keys[r] of the table for the entries of request r. A lane
+// keeps its request word and its row across the hash; the expected ids are loaded after it, where they
+// are compared. Entries of one request are neighbouring lanes, so their key loads mostly hit one line.
+struct MacRequests {
+    const uint32_t* __restrict__ key_states;
+    uint64_t nkeys;
+    const uint32_t* __restrict__ req_keys;
+    RequestIds ids;
+    struct Entry {
+        MacKeyRow k;
+        uint32_t req;
+        const RequestIds& ids;
+        __device__ __forceinline__ bool keyed() const { return k.valid(); }
+        __device__ __forceinline__ const MacKeyRow& key() const { return k; }
+        __device__ __forceinline__ int32_t id_status(const uint32_t* hw, uint64_t i) const {
+            const uint64_t lid = (uint64_t)ids.exp_lid[i], eid = (uint64_t)ids.exp_eid[i];
+            const uint32_t dl = (hw[0] ^ (uint32_t)(lid >> 32)) | (hw[1] ^ (uint32_t)lid);
+            const uint32_t de = (hw[2] ^ (uint32_t)(eid >> 32)) | (hw[3] ^ (uint32_t)eid);
+            return dl ? 3 : ((de && !(req & kReqSkipEntryId)) ? 4 : 0);
+        }
+        __device__ __forceinline__ void failed(uint64_t i) const {
+            const uint32_t r = req & ~kReqSkipEntryId;
+            atomicMin(ids.req_first_bad + r, (unsigned long long)(i - ids.req_first[r]));
+        }
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i) const {
+        const uint32_t req = ids.req_of[i];  // < nreq, whatever the CSR holds (request_expand_kernel)
+        return Entry{MacKeyRow{key_states, nkeys, req_keys[req & ~kReqSkipEntryId]}, req, ids};
+    }
+};
+
+// A staged segment of the host form (bkd_digest_verify_requests_mac_host): the host expanded the requests
+// itself, so entry i has its key row key_of[i], its expected ids and its flag word (bit 31: skip the
+// entry-id check) side by side. No prefix word: a request may straddle two segments, and the host takes
+// each request's prefix from the statuses.
+struct MacExpected {
+    const uint32_t* __restrict__ key_states;
+    uint64_t nkeys;
+    const uint32_t* __restrict__ key_of;
+    const int64_t* __restrict__ exp_lid;
+    const int64_t* __restrict__ exp_eid;
+    const uint32_t* __restrict__ flags;
+    struct Entry {
+        MacKeyRow k;
+        const MacExpected& p;
+        __device__ __forceinline__ bool keyed() const { return k.valid(); }
+        __device__ __forceinline__ const MacKeyRow& key() const { return k; }
+        __device__ __forceinline__ int32_t id_status(const uint32_t* hw, uint64_t i) const {
+            const uint64_t lid = (uint64_t)p.exp_lid[i], eid = (uint64_t)p.exp_eid[i];
+            const uint32_t dl = (hw[0] ^ (uint32_t)(lid >> 32)) | (hw[1] ^ (uint32_t)lid);
+            const uint32_t de = (hw[2] ^ (uint32_t)(eid >> 32)) | (hw[3] ^ (uint32_t)eid);
+            return dl ? 3 : ((de && !(p.flags[i] & kReqSkipEntryId)) ? 4 : 0);
+        }
+        __device__ __forceinline__ void failed(uint64_t) const {}
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i) const {
+        return Entry{MacKeyRow{key_states, nkeys, key_of[i]}, *this};
+    }
+};
+
 // Frame i = [32 B header][20 B mac][payload] (DigestManager.verifyDigest, DigestManager.java:226-283):
-// status 1 too short (or unreadable: out of range or over the cap, which also raises err), 2 the MAC over
-// [0, 32) || [52, len) differs from the stored one, 3 ledger id, 4 entry id (id_checks 0 only);
-// *first_bad (initialised to n by an earlier launch) is lowered to the first failing index.
+// status 1 too short (or unreadable: out of range, over the cap or without a key, which also raises err),
+// 2 the MAC over [0, 32) || [52, len) differs from the stored one, 3 ledger id, 4 entry id; the first
+// failing index lowers the verified-prefix word of `who`.
+template <class Who>
 __global__ void __launch_bounds__(kMacBlock) mac_verify_kernel(
-    MacKey key, int64_t ledger_id, int64_t first_entry_id, int id_checks, const uint8_t* __restrict__ framed,
-    uint64_t size, const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths, uint64_t n,
-    int32_t* __restrict__ status, unsigned long long* first_bad, uint32_t* __restrict__ err) {
+    Who who, const uint8_t* __restrict__ framed, uint64_t size, const uint64_t* __restrict__ offsets,
+    const uint32_t* __restrict__ lengths, uint64_t n, int32_t* __restrict__ status, uint32_t* __restrict__ err) {
     const uint64_t i = (uint64_t)blockIdx.x * kMacBlock + threadIdx.x;
     if (i >= n) return;
     const uint64_t o = offsets[i];
     const uint32_t l = lengths[i];
+    const auto x = who.entry(i);
     int32_t st;
-    if (!mac_readable(o, l, size)) {
+    if (!x.keyed() || !mac_readable(o, l, size)) {
         st = 1;
         atomicOr(err, 1u);
     } else if (l < 52u) {
@@ -215,19 +365,14 @@ __global__ void __launch_bounds__(kMacBlock) mac_verify_kernel(
         uint32_t pre[8], mac[5];
 #pragma unroll
         for (int t = 0; t < 8; ++t) pre[t] = hw[t];
-        mac_entry<true>(key, pre, in, 13u, l - 52u, mac);
+        mac_entry<true>(x.key(), pre, in, 13u, l - 52u, mac);
         uint32_t diff = 0u;
 #pragma unroll
         for (int k = 0; k < 5; ++k) diff |= mac[k] ^ hw[8 + k];
-        const int64_t lid = (int64_t)(((uint64_t)hw[0] << 32) | hw[1]);
-        const int64_t eid = (int64_t)(((uint64_t)hw[2] << 32) | hw[3]);
-        if (diff) st = 2;
-        else if (lid != ledger_id) st = 3;
-        else if (id_checks == 0 && eid != first_entry_id + (int64_t)i) st = 4;
-        else st = 0;
+        st = diff ? 2 : x.id_status(hw, i);
     }
     status[i] = st;
-    if (st != 0) atomicMin(first_bad, (unsigned long long)i);
+    if (st != 0) x.failed(i);
 }
 
 }  // namespace bkd

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import checksum as _ck
 from .bytebuf import CompositeBuffer
-from ._native import (CRC32, CRC32C, VERIFY_DIGEST_MISMATCH, VERIFY_ENTRY_MISMATCH, VERIFY_LEDGER_MISMATCH,
+from ._native import (CRC32, CRC32C, MAC_LENGTH, VERIFY_DIGEST_MISMATCH, VERIFY_ENTRY_MISMATCH, VERIFY_LEDGER_MISMATCH,
                       VERIFY_OK, VERIFY_TOO_SHORT, REFRAME_TRUSTED, check, lib)
 
 METADATA_LENGTH = 32          # DigestManager.java:48
@@ -497,6 +497,125 @@ def package_batch_ledgers_host(digest_type, ledger_ids, entry_ids, lacs, length_
     return _package_frames_host("bkd_digest_package_batch_ledgers_host", (algo,), _mac_of(algo),
                                 np.ascontiguousarray(ledger_ids, dtype=np.int64), entry_ids, lacs, length_fields,
                                 payloads, frame_stride)
+
+
+# ---- MAC ledgers across ledgers: a table of key states and an index per request or per entry ----
+# One GPU lane hashes one MAC entry, so only a batch across thousands of ledgers fills the device, and every
+# MAC ledger has its own password: these calls take uint32[nkeys, 10] key states (``mac_key_table``) where
+# MacDigestManager's batch methods take the one key of their ledger.
+
+def mac_key_table(passwords) -> np.ndarray:
+    """uint32[nkeys, 10]: row k is the key state of a MAC ledger with passwords[k] (``checksum.mac_key_init``).
+    The host forms take it as it is; the device forms take it as a tensor on the device, e.g.
+    ``torch.from_numpy(table.view(np.int32)).to(device)``."""
+    table = np.zeros((len(passwords), 10), dtype=np.uint32)
+    for k, passwd in enumerate(passwords):
+        table[k] = _ck.mac_key_init(passwd)
+    return table
+
+
+def _dev_key_table(key_states, index, name: str, dev, min_numel: int):
+    """(pointer of the device key table, its rows, pointer of the uint32 index tensor)."""
+    u32 = _ck._u32_dtypes()
+    if key_states.numel() % 10:
+        raise ValueError("key_states holds ten words per key (mac_key_table)")
+    return (_ck._dev_ptr(key_states, "key_states", u32, dev), key_states.numel() // 10,
+            _ck._dev_ptr(index, name, u32, dev, min_numel))
+
+
+def _host_key_table(key_states, index, name: str, count: int):
+    """(the table uint32[nkeys, 10] and the index uint32[count] to keep alive, then their C arguments)."""
+    table = np.ascontiguousarray(key_states, dtype=np.uint32)
+    if table.size % 10:
+        raise ValueError("key_states holds ten words per key (mac_key_table)")
+    idx = np.ascontiguousarray(index, dtype=np.uint32)
+    if idx.size != count:
+        raise ValueError(f"{name} has {idx.size} elements, needs {count}")
+    return (table, idx), (ctypes.c_void_p(table.ctypes.data), table.size // 10, ctypes.c_void_p(idx.ctypes.data))
+
+
+def verify_requests_mac(key_states, req_keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids,
+                        skip_flags=None, stream=None):
+    """``verify_requests`` for MAC ledgers (bkd_digest_verify_requests_mac): request r is keyed with row
+    req_keys[r] (int32 / uint32 [nreq]) of key_states (a device tensor of ``mac_key_table``'s words). A key
+    index outside the table gives its entries VERIFY_TOO_SHORT and, like a malformed req_first, raises
+    BKD_ERR_BOUNDS from the stream's next ``stream_sync``. Returns (status int32[n], req_first_bad int64[nreq])."""
+    import torch
+    n = offsets.numel()
+    dev = framed.device
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    if req_first.numel() < 1:
+        raise ValueError("req_first holds nreq + 1 values")
+    nreq = req_first.numel() - 1
+    _check_csr_sizes(nreq, ledger_ids.numel(), first_entry_ids.numel(),
+                     None if skip_flags is None else skip_flags.numel())
+    if skip_flags is None:
+        skip_flags = torch.zeros(nreq, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    req_first_bad = torch.empty(nreq, dtype=torch.int64, device=dev)
+    with _ck._on_device(framed):
+        check(lib().bkd_digest_verify_requests_mac(
+            *_dev_key_table(key_states, req_keys, "req_keys", dev, nreq), _ck._dev_ptr(framed, "framed"),
+            framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
+            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(req_first, "req_first", i64, dev), nreq,
+            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev), _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev),
+            _ck._dev_ptr(skip_flags, "skip_flags", u32, dev), _ck._dev_ptr(status, "status"),
+            _ck._dev_ptr(req_first_bad, "req_first_bad"), _ck._stream_ptr(stream, framed)))
+    return status, req_first_bad
+
+
+def package_batch_ledgers_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
+                              frame_stride=None, stream=None, sync_check: bool = False):
+    """``MacDigestManager.package_batch`` with ledger_ids[i] framing entry i and row key_of[i] of key_states
+    keying it (bkd_digest_package_batch_ledgers_mac): returns (frames[n, frame_stride] uint8, macs uint8[n, 20]).
+    A key index outside the table: the header is written, the MAC bytes are zero, BKD_ERR_BOUNDS from the
+    stream's next sync (here, when ``sync_check``)."""
+    import torch
+    n = offsets.numel()
+    frames, _ = _package_frames("bkd_digest_package_batch_ledgers_mac",
+                                _dev_key_table(key_states, key_of, "key_of", payload.device, n), MAC_LENGTH,
+                                (ledger_ids,), entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride,
+                                None, stream, sync_check, with_digests=False)
+    with _ck._on_device(payload):
+        with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+            macs = frames[:, METADATA_LENGTH:METADATA_LENGTH + MAC_LENGTH].contiguous()
+    return frames, macs
+
+
+def verify_requests_mac_host(key_states, req_keys, frames, req_first, ledger_ids, first_entry_ids, skip_flags=None):
+    """``verify_requests_host`` for MAC ledgers: key_states uint32[nkeys, 10] and req_keys[nreq] in host
+    memory. A key index outside the table or a malformed req_first raises BKD_ERR_INVALID_ARG before any
+    work. Returns (status int32[n], req_first_bad uint64[nreq])."""
+    views, ptrs, lens = _ck._host_entries(frames)
+    n = len(views)
+    first = np.ascontiguousarray(req_first, dtype=np.uint64)
+    if first.size < 1:
+        raise ValueError("req_first holds nreq + 1 values")
+    nreq = first.size - 1
+    lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
+    eids = np.ascontiguousarray(first_entry_ids, dtype=np.int64)
+    flags = np.zeros(nreq, dtype=np.uint32) if skip_flags is None else np.ascontiguousarray(skip_flags, dtype=np.uint32)
+    _check_csr_sizes(nreq, lids.size, eids.size, flags.size)
+    _keep, keys = _host_key_table(key_states, req_keys, "req_keys", nreq)
+    status = np.zeros(n, dtype=np.int32)
+    first_bad = np.zeros(nreq, dtype=np.uint64)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_verify_requests_mac_host(
+        *keys, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first.ctypes.data), nreq, vp(lids.ctypes.data),
+        vp(eids.ctypes.data), vp(flags.ctypes.data), vp(status.ctypes.data), vp(first_bad.ctypes.data)))
+    del views
+    return status, first_bad
+
+
+def package_batch_ledgers_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payloads,
+                                   frame_stride=None):
+    """``MacDigestManager.package_batch_host`` with ledger_ids[i] framing entry i and row key_of[i] keying it:
+    returns (headers uint8[n, frame_stride] = [32 B header][20 B MAC], macs uint8[n, 20])."""
+    _keep, keys = _host_key_table(key_states, key_of, "key_of", len(payloads))
+    frames, _ = _package_frames_host("bkd_digest_package_batch_ledgers_mac_host", keys, MAC_LENGTH,
+                                     np.ascontiguousarray(ledger_ids, dtype=np.int64), entry_ids, lacs, length_fields,
+                                     payloads, frame_stride, with_digests=False)
+    return frames, frames[:, METADATA_LENGTH:METADATA_LENGTH + MAC_LENGTH].copy()
 
 
 # ---- composite payloads (a CompositeByteBuf add: DigestManager.java:62-72, 126-181, 380-392) ----

@@ -517,6 +517,55 @@ BKD_API int bkd_digest_verify_batch_mac_host(const uint32_t* key_state, int64_t 
                                              const uint32_t* h_lengths, uint64_t n, int32_t* h_status,
                                              uint64_t* h_first_bad);
 
+/* MAC batches that span many ledgers. One lane hashes one entry, so the device is full only with some
+ * 260 000 entries in flight, and no single ledger has a batch of that size; a MAC ledger also has its
+ * own password, hence its own key. These calls take a key table — nkeys x 10 uint32_t, row k what
+ * bkd_mac_key_init / bkd_mac_key_state writes, in device memory for the device calls and in host memory
+ * for the _host forms — and an index into it per request (verify) or per entry (package). Several
+ * requests or entries may name one row.
+ *
+ * Verify requests: the CSR, the ledger ids, the first entry ids, BKD_REQUEST_SKIP_ENTRY_ID, d_status and
+ * d_req_first_bad exactly as in bkd_digest_verify_requests (n == 0 writes zeros; nreq == 0 requires
+ * n == 0); frames and status codes exactly as in bkd_digest_verify_batch_mac; request r is keyed with row
+ * d_req_keys[r]. Package: frames as in bkd_digest_package_batch_mac, entry i framed for d_ledger_ids[i]
+ * and keyed with row d_key_of[i].
+ *
+ * A key index >= nkeys on the device: the entry counts as unreadable and is not read — verify gives it
+ * BKD_VERIFY_TOO_SHORT, package writes its header and zero MAC bytes — and the stream's bounds flag is
+ * raised; no row outside the table is loaded. A malformed CSR on the device behaves as in
+ * bkd_digest_verify_requests: the flag is raised, the outputs are unspecified, no access leaves the
+ * caller's arrays. Asynchronous on `stream`, no host synchronisation. */
+BKD_API int bkd_digest_verify_requests_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_req_keys,
+                                           const void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                                           const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first,
+                                           uint64_t nreq, const int64_t* d_req_ledger_ids,
+                                           const int64_t* d_req_first_entry_ids, const uint32_t* d_req_flags,
+                                           int32_t* d_status, uint64_t* d_req_first_bad, void* stream);
+BKD_API int bkd_digest_package_batch_ledgers_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                                 const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                                 const int64_t* d_lacs, const int64_t* d_length_fields,
+                                                 const void* d_payload, uint64_t payload_size,
+                                                 const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                                                 void* d_frames, uint64_t frame_stride, void* stream);
+/* Host-resident forms, shaped as bkd_digest_verify_requests_host / bkd_digest_package_batch_ledgers_host
+ * with the key table, nkeys and the index array (host memory) in front, and no digest words out.
+ * Synchronous; the route as for the MAC host forms above. The index array (every value < nkeys) and the
+ * CSR are checked before any work: a violation returns BKD_ERR_INVALID_ARG and writes nothing. The GPU
+ * route uploads the table once per call and stages entries in segments of at most 64 MiB; a request that
+ * straddles two segments gets the minimum of both parts as its verified prefix. */
+BKD_API int bkd_digest_verify_requests_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_req_keys,
+                                                const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                                                const uint64_t* h_req_first, uint64_t nreq,
+                                                const int64_t* h_req_ledger_ids, const int64_t* h_req_first_entry_ids,
+                                                const uint32_t* h_req_flags, int32_t* h_status,
+                                                uint64_t* h_req_first_bad);
+BKD_API int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint64_t nkeys,
+                                                      const uint32_t* h_key_of, const int64_t* h_ledger_ids,
+                                                      const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                                      const int64_t* h_length_fields, const void* const* h_payloads,
+                                                      const uint32_t* h_lengths, uint64_t n, void* h_frames,
+                                                      uint64_t frame_stride);
+
 /* ---- synthetic input + test helpers --------------------------------------------------- */
 
 /* Fills nbytes of device memory with the little-endian splitmix64 stream
