@@ -115,6 +115,15 @@ PROTOTYPES = {
     "bkd_digest_verify_requests_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "bkd_digest_package_batch_ledgers_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp,
                                                          _u64]),
+    "bkd_digest_package_batch_segments_mac": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64,
+                                                     _vp, _u64, _vp, _u64, _vp]),
+    "bkd_digest_package_batch_v2_mac": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp,
+                                               _u64, _u32, _u32, _vp, _u64, _vp, _vp]),
+    "bkd_digest_package_batch_segments_mac_host": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp,
+                                                          _u64, _vp, _u64]),
+    "bkd_digest_package_batch_v2_mac_host": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64,
+                                                    _u32, _u32, _vp]),
+    "bkd_host_segments_length_capped": (_int, [_vp, _u64, _u64, _c.POINTER(_u64)]),
     "bkd_entrylog_index": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_verify": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),

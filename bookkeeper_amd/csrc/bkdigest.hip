@@ -1648,6 +1648,58 @@ int mac_package(DeviceState& ds, hipStream_t st, const Who& who, const int64_t* 
     return BKD_OK;
 }
 
+// Composite payloads (bkd_digest_package_batch_segments_mac): the package kernel over the entries'
+// segments, one launch; each payload byte is read once and none is copied.
+int mac_package_segments(DeviceState& ds, hipStream_t st, const bkd::MacLedgersOr& who, const int64_t* d_entry_ids,
+                         const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload, uint64_t size,
+                         const uint64_t* d_seg_offsets, const uint32_t* d_seg_lengths, uint64_t nseg,
+                         const uint64_t* d_seg_first, uint64_t n, void* d_frames, uint64_t stride) {
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    const bkd::MacSegments src{(const uint8_t*)d_payload, size, d_seg_offsets, d_seg_lengths, nseg, d_seg_first, n};
+    hipLaunchKernelGGL((bkd::mac_package_adds_kernel<bkd::MacLedgersOr, bkd::MacSegments, bkd::MacFrames>),
+                       dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who, d_entry_ids, d_lacs, d_length_fields, src, n,
+                       bkd::MacFrames{(uint8_t*)d_frames, stride}, err);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
+// V2 add requests (bkd_digest_package_batch_v2_mac): the package kernel writes every request's 80-byte head
+// and, into the stream's scratch (slot 3, package_v2's), the bytes to copy in behind it; then
+// package_v2_copy_kernel as for the CRC digests, with those lengths. Two launches, no host sync.
+int mac_package_v2(DeviceState& ds, hipStream_t st, const bkd::MacLedgersOr& who, const int64_t* d_entry_ids,
+                   const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload, uint64_t size,
+                   const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, const uint8_t* d_keys,
+                   uint64_t key_stride, uint32_t packet_header, uint32_t small_threshold, void* d_requests,
+                   uint64_t requests_size, const uint64_t* d_request_offsets) {
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // the scratch and the two launches as one sequence
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    uint8_t* sb = nullptr;
+    const hipError_t e = sc.get(3, (size_t)n * 4, st, &sb);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("package_v2 scratch: ") + hipGetErrorString(e));
+    uint32_t* copy_len = reinterpret_cast<uint32_t*>(sb);
+    const bkd::V2Requests rq{(uint8_t*)d_requests, requests_size, d_request_offsets, bkd::host::kMacLen, small_threshold};
+    hipLaunchKernelGGL((bkd::mac_package_adds_kernel<bkd::MacLedgersOr, bkd::MacRanges, bkd::MacV2Heads>), dim3(mac_blocks(n)),
+                       dim3(bkd::kMacBlock), 0, st, who, d_entry_ids, d_lacs, d_length_fields,
+                       bkd::MacRanges{(const uint8_t*)d_payload, size, d_offsets, d_lengths}, n,
+                       bkd::MacV2Heads{rq, d_keys, key_stride, packet_header, copy_len}, err);
+    BKD_HIP(hipGetLastError());
+    if (small_threshold == 0u) return BKD_OK;
+    return with_lanes<4>(v2_copy_lanes(size / n), [&](auto g) -> int {
+        constexpr int G = decltype(g)::value;
+        const uint64_t per_block = 256 / G;
+        const unsigned cblocks = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, 8u * (uint64_t)ds.cus);
+        hipLaunchKernelGGL(bkd::package_v2_copy_kernel<G>, dim3(cblocks), dim3(256), 0, st, (const uint8_t*)d_payload, size,
+                           d_offsets, copy_len, n, rq);
+        BKD_HIP(hipGetLastError());
+        return BKD_OK;
+    });
+}
+
 // *d_first_bad = n (reframe_first_bad_kernel, as the trusted reframe initialises it), then the verify
 // kernel lowers it.
 int mac_verify(DeviceState& ds, hipStream_t st, const uint32_t* key_state, int64_t ledger_id, int64_t first_entry_id,
@@ -2838,6 +2890,189 @@ int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint
     };
     return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch, hl, false,
                                host_frames(hl, hl, h_frames, frame_stride, nullptr));
+}
+
+int bkd_digest_package_batch_segments_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                          int64_t ledger_id, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                          const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                          uint64_t payload_size, const uint64_t* d_seg_offsets,
+                                          const uint32_t* d_seg_lengths, uint64_t nseg, const uint64_t* d_seg_first,
+                                          uint64_t n, void* d_frames, uint64_t frame_stride, void* stream) {
+    if (n == 0) return BKD_OK;
+    if (!d_entry_ids || !d_lacs || !d_length_fields || !d_seg_first || !d_frames ||
+        (nseg && (!d_seg_offsets || !d_seg_lengths)))
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !d_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (nseg && !d_payload && payload_size) return fail(BKD_ERR_INVALID_ARG, "null payload");
+    if (int rc = check_frame_stride(bkd::host::kMacFrameHead, frame_stride, false)) return rc;
+    if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return mac_package_segments(*call.ds, call.st, bkd::MacLedgersOr{d_key_states, nkeys, d_key_of, d_ledger_ids, ledger_id},
+                                d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size, d_seg_offsets,
+                                d_seg_lengths, nseg, d_seg_first, n, d_frames, frame_stride);
+}
+
+int bkd_digest_package_batch_v2_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                    int64_t ledger_id, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                    const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                    uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                                    uint64_t n, const uint8_t* d_master_keys, uint64_t key_stride, uint32_t flags,
+                                    uint32_t small_threshold, void* d_requests, uint64_t requests_size,
+                                    const uint64_t* d_request_offsets, void* stream) {
+    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
+    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (n == 0) return BKD_OK;
+    if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_master_keys || !d_requests ||
+        !d_request_offsets)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !d_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return mac_package_v2(*call.ds, call.st, bkd::MacLedgersOr{d_key_states, nkeys, d_key_of, d_ledger_ids, ledger_id},
+                          d_entry_ids, d_lacs, d_length_fields, d_payload, payload_size, d_offsets, d_lengths, n,
+                          d_master_keys, key_stride, bkd::host::v2_packet_header(flags), small_threshold, d_requests,
+                          requests_size, d_request_offsets);
+}
+
+namespace {
+
+// The key rows and ledger ids of a host-resident composite or V2 MAC call as the arrays the many-ledger
+// device sequence takes: the caller's, or row 0 / ledger_id for every entry where it passed none. The key
+// indices are checked against the table here, before any work.
+struct MacHostIds {
+    std::vector<uint32_t> rows;
+    std::vector<int64_t> lids;
+    const uint32_t* key_of;
+    const int64_t* ledger_ids;
+    int rc = BKD_OK;
+    MacHostIds(uint64_t nkeys, const uint32_t* h_key_of, int64_t ledger_id, const int64_t* h_ledger_ids, uint64_t n)
+        : key_of(h_key_of), ledger_ids(h_ledger_ids) {
+        if (!h_key_of && nkeys == 0) rc = fail(BKD_ERR_INVALID_ARG, "an empty key table");
+        for (uint64_t i = 0; h_key_of && i < n && !rc; ++i)
+            if (h_key_of[i] >= nkeys)
+                rc = fail(BKD_ERR_INVALID_ARG, "entry " + std::to_string(i) + " names a key outside the table");
+    }
+    // the GPU route's arrays, made only there
+    void materialise(int64_t ledger_id, uint64_t n) {
+        if (!key_of) {
+            rows.assign(n, 0u);
+            key_of = rows.data();
+        }
+        if (!ledger_ids) {
+            lids.assign(n, ledger_id);
+            ledger_ids = lids.data();
+        }
+    }
+};
+
+}  // namespace
+
+int bkd_digest_package_batch_segments_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
+                                               int64_t ledger_id, const int64_t* h_ledger_ids,
+                                               const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                               const int64_t* h_length_fields, const void* const* h_seg_ptrs,
+                                               const uint32_t* h_seg_lengths, uint64_t nseg, const uint64_t* h_seg_first,
+                                               uint64_t n, void* h_frames, uint64_t frame_stride) {
+    if (n == 0) return BKD_OK;
+    if (!h_entry_ids || !h_lacs || !h_length_fields || !h_frames) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    constexpr uint64_t hl = bkd::host::kMacFrameHead;
+    if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
+    MacHostIds ids(nkeys, h_key_of, ledger_id, h_ledger_ids, n);  // before any work, so no frame is written
+    if (ids.rc) return ids.rc;
+    if (int rc = check_host_segments(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n)) return rc;
+    const HostSegments segs(h_seg_ptrs, h_seg_lengths, nseg, h_seg_first, n);
+    const int route = mac_host_route(segs.entry_len.data(), n);
+    if (route < 0) return route;
+    if (route == 1) {
+        bkd::host::mac_package_frames_segments(h_key_states, h_key_of, ledger_id, h_ledger_ids, h_entry_ids, h_lacs,
+                                               h_length_fields, (const uint8_t* const*)h_seg_ptrs, h_seg_lengths,
+                                               h_seg_first, segs.entry_len.data(), n, (uint8_t*)h_frames, frame_stride);
+        return BKD_OK;
+    }
+    // each entry's segments end to end in the staging buffer (HostSegments: an entry is never split between
+    // two staged segments), then bkd_digest_package_batch_ledgers_mac's device sequence
+    ids.materialise(ledger_id, n);
+    DeviceTable keys;  // uploaded once, by the first segment (the staged call has entered the device by then)
+    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        int r = keys.upload(h_key_states, nkeys);
+        if (r) return r;
+        r = segs(hs, s, i0, cnt, bytes);
+        if (r) return r;
+        memcpy(hs.h_seed[s], ids.key_of + i0, cnt * 4);
+        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+        return BKD_OK;
+    };
+    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
+                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
+        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
+                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
+    };
+    return package_host_staged(ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, segs.entry_len.data(), n, launch,
+                               hl, false, host_frames(hl, hl, h_frames, frame_stride, nullptr));
+}
+
+int bkd_digest_package_batch_v2_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
+                                         int64_t ledger_id, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                                         const int64_t* h_lacs, const int64_t* h_length_fields,
+                                         const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
+                                         const uint8_t* h_master_keys, uint64_t key_stride, uint32_t flags,
+                                         uint32_t small_threshold, void* const* h_requests) {
+    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
+    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (n == 0) return BKD_OK;
+    if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_master_keys || !h_requests)
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+        if (!h_requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
+    }
+    MacHostIds ids(nkeys, h_key_of, ledger_id, h_ledger_ids, n);  // before any work, so no request is written
+    if (ids.rc) return ids.rc;
+    const int route = mac_host_route(h_lengths, n);
+    if (route < 0) return route;
+    const bkd::host::MacV2Head head{h_master_keys, key_stride, bkd::host::v2_packet_header(flags), small_threshold};
+    const uint8_t* const* payloads = (const uint8_t* const*)h_payloads;
+    uint8_t* const* requests = (uint8_t* const*)h_requests;
+    if (route == 1) {
+        bkd::host::mac_package_requests_v2(h_key_states, h_key_of, ledger_id, h_ledger_ids, h_entry_ids, h_lacs,
+                                           h_length_fields, payloads, h_lengths, n, head, requests);
+        return BKD_OK;
+    }
+    // GPU: staged and packaged into 52-byte frames as bkd_digest_package_batch_ledgers_mac_host; each finished
+    // segment's frames go into the requests behind the prefix the host writes, the small payloads from their
+    // sources
+    ids.materialise(ledger_id, n);
+    DeviceTable keys;
+    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        int r = keys.upload(h_key_states, nkeys);
+        if (r) return r;
+        r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        memcpy(hs.h_seed[s], ids.key_of + i0, cnt * 4);
+        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+        return BKD_OK;
+    };
+    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
+                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
+        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
+                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
+    };
+    constexpr uint64_t hl = bkd::host::kMacFrameHead;
+    return package_host_staged(ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch, hl, false,
+                               [&](const uint8_t* frm, const uint32_t*, uint64_t i0, uint64_t cnt) {
+                                   bkd::host::mac_finish_requests_v2(frm, payloads + i0, h_lengths + i0, cnt, head, i0,
+                                                                     requests + i0);
+                               });
+}
+
+int bkd_host_segments_length_capped(const uint32_t* h_seg_lengths, uint64_t nseg, uint64_t cap, uint64_t* bytes) {
+    const bkd::SegLength r = bkd::segments_length_capped(h_seg_lengths, 0, nseg, cap);
+    if (bytes) *bytes = r.bytes;
+    return r.over ? 1 : 0;
 }
 
 int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,

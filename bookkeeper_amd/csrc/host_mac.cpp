@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "host_batch.hpp"
+#include "mac_segments.hpp"
 #include "mac_sha1.hpp"
 
 namespace bkd {
@@ -178,6 +179,96 @@ void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_
     each_entry(n, lens, [&](uint64_t i) {
         mac_package_one(key_states + (uint64_t)key_of[i] * 10u, ledger_ids[i], entry_ids[i], lacs[i], length_fields[i],
                         payloads[i], lens[i], frames + i * stride);
+    });
+}
+
+// ---- composite entries and V2 add requests ----
+
+namespace {
+
+struct HostKey {
+    const uint32_t* s;
+    const uint32_t* inner() const { return s; }
+    const uint32_t* outer() const { return s + 5; }
+};
+
+// The non-empty segments [k, k1) in order, for the walker.
+struct HostCursor {
+    const uint8_t* const* ptrs;
+    const uint32_t* lens;
+    uint64_t k, k1;
+    bool next(const uint8_t*& p, uint32_t& len) {
+        for (; k < k1; ++k)
+            if (lens[k]) {
+                p = ptrs[k];
+                len = lens[k];
+                ++k;
+                return true;
+            }
+        return false;
+    }
+};
+
+inline void put_header(uint8_t* f, int64_t ledger_id, int64_t entry_id, int64_t lac, int64_t length_field) {
+    put_be64(f, (uint64_t)ledger_id);
+    put_be64(f + 8, (uint64_t)entry_id);
+    put_be64(f + 16, (uint64_t)lac);
+    put_be64(f + 24, (uint64_t)length_field);
+}
+
+inline void put_v2_prefix(uint8_t* r, uint32_t len, const MacV2Head& head, uint64_t i) {
+    put_be32(r, kMacV2Head - 4u + len);  // Java int arithmetic
+    put_be32(r + 4, head.packet_header);
+    memcpy(r + 8, head.keys + i * head.key_stride, 20);
+}
+
+}  // namespace
+
+void mac_one_segments(const uint32_t* key_state, const uint8_t* pre32, const uint8_t* const* seg_ptrs,
+                      const uint32_t* seg_lens, uint64_t k0, uint64_t k1, uint8_t* out20) {
+    uint64_t total = 0;
+    for (uint64_t k = k0; k < k1; ++k) total += seg_lens[k];
+    uint32_t pre[8], mac[5];
+    for (int t = 0; t < 8; ++t) pre[t] = be32(pre32 + 4 * t);
+    HostCursor segs{seg_ptrs, seg_lens, k0, k1};
+    macseg::hmac(HostKey{key_state}, pre, segs, total, macseg::HostLoad{}, mac);
+    for (int k = 0; k < 5; ++k) put_be32(out20 + 4 * k, mac[k]);
+}
+
+void mac_package_frames_segments(const uint32_t* key_states, const uint32_t* key_of, int64_t ledger_id,
+                                 const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                                 const int64_t* length_fields, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens,
+                                 const uint64_t* seg_first, const uint32_t* entry_lens, uint64_t n, uint8_t* frames,
+                                 uint64_t stride) {
+    each_entry(n, entry_lens, [&](uint64_t i) {
+        uint8_t* f = frames + i * stride;
+        put_header(f, ledger_ids ? ledger_ids[i] : ledger_id, entry_ids[i], lacs[i], length_fields[i]);
+        mac_one_segments(key_states + (uint64_t)(key_of ? key_of[i] : 0u) * 10u, f, seg_ptrs, seg_lens, seg_first[i],
+                         seg_first[i + 1], f + 32);
+    });
+}
+
+void mac_package_requests_v2(const uint32_t* key_states, const uint32_t* key_of, int64_t ledger_id,
+                             const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                             const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                             uint64_t n, const MacV2Head& head, uint8_t* const* requests) {
+    each_entry(n, lens, [&](uint64_t i) {
+        uint8_t* r = requests[i];
+        put_v2_prefix(r, lens[i], head, i);
+        mac_package_one(key_states + (uint64_t)(key_of ? key_of[i] : 0u) * 10u, ledger_ids ? ledger_ids[i] : ledger_id,
+                        entry_ids[i], lacs[i], length_fields[i], payloads[i], lens[i], r + 28);
+        // copied while the hash has it in the cache (isSmallEntry, DigestManager.java:128, 160-163)
+        if (lens[i] && lens[i] < head.small) memcpy(r + kMacV2Head, payloads[i], lens[i]);
+    });
+}
+
+void mac_finish_requests_v2(const uint8_t* frames, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
+                            const MacV2Head& head, uint64_t first, uint8_t* const* requests) {
+    each_entry(n, lens, [&](uint64_t i) {
+        uint8_t* r = requests[i];
+        put_v2_prefix(r, lens[i], head, first + i);
+        memcpy(r + 28, frames + i * kMacFrameHead, kMacFrameHead);
+        if (lens[i] && lens[i] < head.small) memcpy(r + kMacV2Head, payloads[i], lens[i]);
     });
 }
 

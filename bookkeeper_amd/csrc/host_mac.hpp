@@ -46,5 +46,40 @@ void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_
                                 const uint8_t* const* payloads, const uint32_t* lens, uint64_t n, uint8_t* frames,
                                 uint64_t stride);
 
+// Composite entries and V2 add requests (bkd_digest_package_batch_segments_mac_host,
+// bkd_digest_package_batch_v2_mac_host). key_of (may be null: row 0 for all) and ledger_ids (may be null:
+// ledger_id for all) as above.
+// out20 = HMAC over pre[0, 32) || the non-empty segments ptrs[k], k in [k0, k1), in order: the segment
+// walker the device kernel runs (mac_segments.hpp) over the segments' own bytes, nothing joined. No byte
+// outside a segment is read.
+void mac_one_segments(const uint32_t* key_state, const uint8_t* pre32, const uint8_t* const* seg_ptrs,
+                      const uint32_t* seg_lens, uint64_t k0, uint64_t k1, uint8_t* out20);
+// Entry i = segments seg_first[i] .. seg_first[i + 1] - 1, each its own host buffer; entry_lens[i] its
+// bytes (saturated at 2^32 - 1: only the work is split by it). Frames as mac_package_frames_ledgers.
+void mac_package_frames_segments(const uint32_t* key_states, const uint32_t* key_of, int64_t ledger_id,
+                                 const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                                 const int64_t* length_fields, const uint8_t* const* seg_ptrs, const uint32_t* seg_lens,
+                                 const uint64_t* seg_first, const uint32_t* entry_lens, uint64_t n, uint8_t* frames,
+                                 uint64_t stride);
+// Request i into requests[i]: [int32 BE 76 + len][int32 BE packet header][20 B key][32 B header][20 B mac]
+// and the payload behind it when it is shorter than `small`, copied right after it is hashed. keys: entry
+// i's 20-byte master key at keys + i * key_stride.
+struct MacV2Head {
+    const uint8_t* keys;
+    uint64_t key_stride;
+    uint32_t packet_header;
+    uint32_t small;
+};
+constexpr uint32_t kMacV2Head = 28 + kMacFrameHead;  // 80 bytes in front of the payload
+void mac_package_requests_v2(const uint32_t* key_states, const uint32_t* key_of, int64_t ledger_id,
+                             const int64_t* ledger_ids, const int64_t* entry_ids, const int64_t* lacs,
+                             const int64_t* length_fields, const uint8_t* const* payloads, const uint32_t* lens,
+                             uint64_t n, const MacV2Head& head, uint8_t* const* requests);
+// The GPU route's last step for entries [first, first + n) (the arrays start at entry `first`, the keys at
+// entry 0): the prefix, frame i of the packed 52-byte frames the device returned, and the small payloads
+// from their sources.
+void mac_finish_requests_v2(const uint8_t* frames, const uint8_t* const* payloads, const uint32_t* lens, uint64_t n,
+                            const MacV2Head& head, uint64_t first, uint8_t* const* requests);
+
 }  // namespace host
 }  // namespace bkd

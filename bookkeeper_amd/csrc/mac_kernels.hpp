@@ -19,13 +19,24 @@
 // a kernel argument (SGPRs); MacLedgers / MacRequests index a table of key states in device memory, so a
 // batch spans ledgers with a key each. A table row's inner words are loaded into the hash state before
 // the first block and its outer words only after the inner hash, so neither is held across the rounds.
+//
+// Sources and destinations. The package body (mac_package_lane) is also a template over where an entry's
+// bytes lie (MacRanges: one range of the payload; MacSegments: the entry's segments, hashed as one stream
+// by the walker of mac_segments.hpp, which the host route shares) and over what is written for it
+// (MacFrames: a frame at a stride; MacV2Heads: the 80-byte head of a V2 add request);
+// mac_package_adds_kernel launches it for the composite and V2 calls. The kernel is ALU-bound — some
+// 40 000 VALU instructions per 4 KiB entry — so the lane that hashed an entry stores its frame or head
+// itself; the reason the CRC streaming kernels keep their frame stores in a pass of their own (stores
+// between the loads of a bandwidth-bound loop) does not apply.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/bkdigest.h"
 #include "crc_kernels.hpp"
+#include "mac_segments.hpp"
 #include "mac_sha1.hpp"
+#include "plan_kernels.hpp"
 
 namespace bkd {
 
@@ -215,10 +226,203 @@ struct MacLedgers {
     }
 };
 
-// frames + i * stride = [ledger id, entry_ids[i], lacs[i], length_fields[i] as BE longs][20 B mac]
-// (DigestManager.java:146-155, 172-178); no other byte of the stride is written. An unreadable payload
-// (out of range, over the cap, or without a key): the header is written, the MAC bytes are zero, err is
-// raised.
+// MacLedgers for the composite and V2 calls (bkd_digest_package_batch_segments_mac, _v2_mac), whose index
+// arrays are optional: a null key_of keys every entry with row 0, a null ledger_ids frames every entry
+// for ledger_id.
+struct MacLedgersOr {
+    const uint32_t* __restrict__ key_states;
+    uint64_t nkeys;
+    const uint32_t* __restrict__ key_of;
+    const int64_t* __restrict__ ledger_ids;
+    int64_t ledger_id;
+    __device__ __forceinline__ MacLedgers::Entry entry(uint64_t i) const {
+        return MacLedgers::Entry{MacKeyRow{key_states, nkeys, key_of ? key_of[i] : 0u},
+                                 ledger_ids ? ledger_ids[i] : ledger_id};
+    }
+};
+
+// ---- where entry i of a package call lies ------------------------------------------------------------
+//   const auto e = src.entry(i, err);   (a malformed index raises err here)
+//   e.readable()            in range and under the cap: the only entries that are read
+//   e.length()              its bytes
+//   e.hash(key, hdr, mac)   mac[5] = HMAC(hdr || the entry's bytes)
+
+// One range of the payload per entry (bkd_digest_package_batch_mac, _ledgers_mac, _v2_mac).
+struct MacRanges {
+    const uint8_t* __restrict__ payload;
+    uint64_t size;
+    const uint64_t* __restrict__ offsets;
+    const uint32_t* __restrict__ lengths;
+    struct Entry {
+        const uint8_t* __restrict__ payload;
+        uint64_t size, o;
+        uint32_t l;
+        __device__ __forceinline__ bool readable() const { return mac_readable(o, l, size); }
+        __device__ __forceinline__ uint32_t length() const { return l; }
+        template <class Key>
+        __device__ __forceinline__ void hash(const Key& key, const uint32_t (&hdr)[8], uint32_t (&mac)[5]) const {
+            const MacStream in(payload + o, l);
+            mac_entry<true>(key, hdr, in, 0u, l, mac);
+        }
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i, uint32_t*) const {
+        return Entry{payload, size, offsets[i], lengths[i]};
+    }
+};
+
+// The load primitive of the segment walker on the device: the aligned dword itself. The walker asks only
+// for dwords that hold a byte of the segment.
+struct MacDwordLoad {
+    __device__ __forceinline__ uint32_t operator()(const uint8_t* at, const uint8_t*, uint32_t) const {
+        return *(const uint32_t*)at;
+    }
+};
+
+// The entry's segments (bkd_digest_package_batch_segments_mac): entry i = segments first[i] ..
+// first[i + 1] - 1 of the CSR, clamped by segments_range (a malformed one raises err), empty ones skipped.
+// Its length is their 64-bit sum, given up once it passes the cap (segments_length_capped); an entry
+// over the cap or with a non-empty segment out of range is unreadable, and none of its bytes is loaded.
+struct MacSegments {
+    const uint8_t* __restrict__ payload;
+    uint64_t size;
+    const uint64_t* __restrict__ seg_offsets;
+    const uint32_t* __restrict__ seg_lengths;
+    uint64_t nseg;
+    const uint64_t* __restrict__ first;
+    uint64_t n;
+    // The non-empty segments of one entry in order, for the walker.
+    struct Cursor {
+        const uint8_t* __restrict__ payload;
+        const uint64_t* __restrict__ seg_offsets;
+        const uint32_t* __restrict__ seg_lengths;
+        uint64_t k, k1;
+        __device__ __forceinline__ bool next(const uint8_t*& p, uint32_t& len) {
+            while (k < k1) {
+                len = seg_lengths[k];
+                const uint64_t o = seg_offsets[k];
+                ++k;
+                if (len) {
+                    p = payload + o;
+                    return true;
+                }
+            }
+            return false;
+        }
+    };
+    struct Entry {
+        const MacSegments& s;
+        uint64_t k0, k1;
+        uint32_t total;
+        bool ok;
+        __device__ __forceinline__ bool readable() const { return ok; }
+        __device__ __forceinline__ uint32_t length() const { return total; }
+        template <class Key>
+        __device__ __forceinline__ void hash(const Key& key, const uint32_t (&hdr)[8], uint32_t (&mac)[5]) const {
+            Cursor segs{s.payload, s.seg_offsets, s.seg_lengths, k0, k1};
+            macseg::hmac(key, hdr, segs, total, MacDwordLoad{}, mac);
+        }
+    };
+    __device__ __forceinline__ Entry entry(uint64_t i, uint32_t* err) const {
+        const SegRange sr = segments_range(first[i], first[i + 1], i, n, nseg);
+        if (sr.bad) atomicOr(err, 1u);
+        const SegLength sl = segments_length_capped(seg_lengths, sr.k0, sr.k1, BKD_MAC_MAX_ENTRY);
+        bool ok = !sl.over;
+        if (ok) {
+            for (uint64_t k = sr.k0; k < sr.k1; ++k) {
+                const uint32_t len = seg_lengths[k];
+                if (!len) continue;  // an empty segment is skipped wherever it says it lies
+                const uint64_t o = seg_offsets[k];
+                ok = ok && o <= size && (uint64_t)len <= size - o;
+            }
+        }
+        return Entry{*this, sr.k0, sr.k1, (uint32_t)sl.bytes, ok};
+    }
+};
+
+// ---- what is written for entry i of a package call ---------------------------------------------------
+//   dst.store(i, len, hashed, hdr, mac, err)   hashed: the entry was read (mac holds zeros otherwise)
+
+// frames + i * stride = [32 B header][20 B mac]; no other byte of the stride is written.
+struct MacFrames {
+    uint8_t* __restrict__ frames;
+    uint64_t stride;
+    __device__ __forceinline__ void store(uint64_t i, uint32_t, bool, const uint32_t (&hdr)[8], const uint32_t (&mac)[5],
+                                          uint32_t*) const {
+        uint8_t* f = frames + i * stride;
+        store_be_words(f, hdr);
+        store_be_words(f + 32, mac);
+    }
+};
+
+// The head of V2 add request i (bkd_digest_package_batch_v2_mac; the layout of package_v2_head_kernel
+// with a 20-byte digest): [int32 BE 76 + len][int32 BE packet header][20 B master key][32 B header]
+// [20 B mac], 80 bytes as twenty big-endian words, by dword stores when the request is 4-byte aligned and
+// by bytes otherwise. A request that does not fit the request buffer raises err and is left alone.
+// copy_len[i] = the bytes package_v2_copy_kernel is to copy in behind the head: len for an entry that was
+// hashed, 0 for an unreadable one (the copy kernel itself skips lengths at or over the threshold).
+struct MacV2Heads {
+    V2Requests rq;
+    const uint8_t* __restrict__ keys;
+    uint64_t key_stride;
+    uint32_t packet_header;
+    uint32_t* __restrict__ copy_len;
+    __device__ __forceinline__ void store(uint64_t i, uint32_t len, bool hashed, const uint32_t (&hdr)[8],
+                                          const uint32_t (&mac)[5], uint32_t* err) const {
+        copy_len[i] = hashed ? len : 0u;
+        uint8_t* r = rq.at(i, hashed ? len : 0u);
+        if (!r) {
+            atomicOr(err, 1u);
+            return;
+        }
+        uint32_t w[20];
+        w[0] = rq.head() - 4u + len;  // headersSize + payloadSize (Java int arithmetic)
+        w[1] = packet_header;
+        const uint8_t* key = keys + i * key_stride;
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            w[2 + k] = ((uint32_t)key[4 * k] << 24) | ((uint32_t)key[4 * k + 1] << 16) | ((uint32_t)key[4 * k + 2] << 8) |
+                       (uint32_t)key[4 * k + 3];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[7 + k] = hdr[k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) w[15 + k] = mac[k];
+        store_be_words(r, w);
+    }
+};
+
+// Entry i's header [ledger id, entry_ids[i], lacs[i], length_fields[i] as BE longs] and the MAC over it
+// and the entry's bytes (DigestManager.java:146-155, 172-178), written where dst puts them. An unreadable
+// entry (out of range, over the cap, or without a key): the header is written, the MAC bytes are zero,
+// err is raised.
+template <class Who, class Src, class Dst>
+__device__ __forceinline__ void mac_package_lane(const Who& who, const int64_t* __restrict__ entry_ids,
+                                                 const int64_t* __restrict__ lacs,
+                                                 const int64_t* __restrict__ length_fields, const Src& src, uint64_t n,
+                                                 const Dst& dst, uint32_t* __restrict__ err) {
+    const uint64_t i = (uint64_t)blockIdx.x * kMacBlock + threadIdx.x;
+    if (i >= n) return;
+    const auto e = src.entry(i, err);
+    const auto x = who.entry(i);
+    const uint64_t f4[4] = {(uint64_t)x.ledger_id(), (uint64_t)entry_ids[i], (uint64_t)lacs[i],
+                            (uint64_t)length_fields[i]};
+    uint32_t hdr[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        hdr[2 * k] = (uint32_t)(f4[k] >> 32);
+        hdr[2 * k + 1] = (uint32_t)f4[k];
+    }
+    uint32_t mac[5] = {0u, 0u, 0u, 0u, 0u};
+    const bool hashed = x.keyed() && e.readable();
+    if (hashed) e.hash(x.key(), hdr, mac);
+    else atomicOr(err, 1u);
+    dst.store(i, e.length(), hashed, hdr, mac, err);
+}
+
+// One range per entry into frames at a stride — MacRanges into MacFrames — with its arguments flat, as the
+// single-ledger and many-ledger package calls have always launched it. It keeps its own body: through
+// mac_package_lane the compiler scheduled the same work differently (2 690 -> 2 645 instructions for
+// MacLedgers), and these two instantiations are to stay the machine code they were
+// (profiles/mac_adds_kernel_disasm.txt).
 template <class Who>
 __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
     Who who, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
@@ -248,6 +452,14 @@ __global__ void __launch_bounds__(kMacBlock) mac_package_kernel(
     uint8_t* f = frames + i * stride;
     store_be_words(f, hdr);
     store_be_words(f + 32, mac);
+}
+
+// Any source into any destination: the composite and V2 calls.
+template <class Who, class Src, class Dst>
+__global__ void __launch_bounds__(kMacBlock) mac_package_adds_kernel(
+    Who who, const int64_t* __restrict__ entry_ids, const int64_t* __restrict__ lacs,
+    const int64_t* __restrict__ length_fields, Src src, uint64_t n, Dst dst, uint32_t* __restrict__ err) {
+    mac_package_lane(who, entry_ids, lacs, length_fields, src, n, dst, err);
 }
 
 // ---- who keys frame i of a verify call and what it must carry ---------------------------------------

@@ -719,6 +719,24 @@ __host__ __device__ inline SegRange segments_range(uint64_t first_i, uint64_t fi
     return r;
 }
 
+// The bytes of a composite entry whose length is capped (bkd_digest_package_batch_segments_mac: one lane
+// hashes the whole entry): the 64-bit sum of seg_lengths[k0, k1), given up as soon as it passes cap. The
+// sum never exceeds cap + 2^32 - 1, so it cannot wrap — 257 listings of one 16 MiB segment are over the
+// cap, not 4 GiB that look like 0 to a 32-bit length. Host and device (bkd_host_segments_length_capped).
+struct SegLength {
+    uint64_t bytes;  // the sum where it stopped: the entry's length when !over
+    bool over;
+};
+__host__ __device__ inline SegLength segments_length_capped(const uint32_t* seg_lengths, uint64_t k0, uint64_t k1,
+                                                            uint64_t cap) {
+    SegLength r{0u, false};
+    for (uint64_t k = k0; k < k1 && !r.over; ++k) {
+        r.bytes += seg_lengths[k];
+        r.over = r.bytes > cap;
+    }
+    return r;
+}
+
 // A segment the join kernel folds itself, byte by byte: in range and shorter than 16 bytes. The indexed
 // path's short-entry launch loads the whole 16-byte block at offset & ~15 of such an entry, an empty one
 // included (small_geo / small_load_idx, crc_kernels.hpp), which for a segment at the very end of the

@@ -713,7 +713,16 @@ V2_PREFIX_LENGTH = 4 + 4 + MASTER_KEY_LENGTH  # the two ints and the master key 
 def request_sizes_v2(algo: int, lengths, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD):
     """Bytes of each V2 request buffer (bufferSize, DigestManager.java:135): 60 + mac, and the payload
     when it is shorter than `small_threshold`. `lengths`: a numpy array or a torch tensor."""
-    head = V2_PREFIX_LENGTH + METADATA_LENGTH + _mac_of(algo)
+    return _request_sizes(V2_PREFIX_LENGTH + METADATA_LENGTH + _mac_of(algo), lengths, small_threshold)
+
+
+def request_sizes_v2_mac(lengths, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD):
+    """``request_sizes_v2`` for MAC ledgers: an 80-byte head (28 + 32 + the 20-byte MAC), and the payload
+    when it is shorter than `small_threshold`."""
+    return _request_sizes(V2_PREFIX_LENGTH + METADATA_LENGTH + MAC_LENGTH, lengths, small_threshold)
+
+
+def _request_sizes(head: int, lengths, small_threshold: int):
     if isinstance(lengths, np.ndarray):
         l = lengths.astype(np.int64)
         return head + np.where(l < small_threshold, l, 0)
@@ -825,6 +834,161 @@ def package_batch_v2_host(digest_type, ledger_ids, entry_ids, lacs, length_field
         raise ValueError("ledger_ids holds one ledger id per entry")
     return _package_v2_host(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key,
                             key_stride, flags, small_threshold)
+
+
+# ---- MAC adds: composite payloads and V2 add requests across ledgers ----
+# The parameters of their CRC namesakes with the key table and the per-entry key rows in front.
+# key_of None: row 0 keys every entry; ledger_ids None: `ledger_id` frames every entry.
+
+def package_batch_segments_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets,
+                               seg_lengths, seg_first, frame_stride=None, out_frames=None, stream=None,
+                               sync_check: bool = False, ledger_id: int = 0):
+    """``package_batch_segments`` for MAC ledgers (bkd_digest_package_batch_segments_mac): entry i is the
+    segments seg_first[i] .. seg_first[i + 1] - 1 of `payload`, hashed as one byte stream by one lane, keyed
+    with row key_of[i] of key_states and framed for ledger_ids[i]. Returns (frames[n, frame_stride] uint8,
+    macs uint8[n, 20]). An entry with a key index outside the table, a segment out of range or more than
+    MAC_MAX_ENTRY bytes is not read: its header is written, its MAC bytes are zero, BKD_ERR_BOUNDS from the
+    stream's next sync (here, when ``sync_check``)."""
+    import torch
+    if seg_first.numel() < 1:
+        raise ValueError("seg_first holds n + 1 values")
+    n = seg_first.numel() - 1
+    nseg = seg_offsets.numel()
+    if seg_lengths.numel() != nseg:
+        raise ValueError("seg_offsets/seg_lengths size mismatch")
+    hl = METADATA_LENGTH + MAC_LENGTH
+    stride = frame_stride or hl
+    dev = payload.device
+    if out_frames is None:
+        out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    elif stride >= hl and n and out_frames.numel() * out_frames.element_size() < (n - 1) * stride + hl:
+        raise ValueError("out_frames is too small for n frames at this stride")
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(lib().bkd_digest_package_batch_segments_mac(
+            *_dev_key_table(key_states, key_of, "key_of", dev, n), ledger_id,
+            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
+            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
+            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
+            _ck._dev_ptr(seg_offsets, "seg_offsets", i64, dev), _ck._dev_ptr(seg_lengths, "seg_lengths", u32, dev), nseg,
+            _ck._dev_ptr(seg_first, "seg_first", i64, dev), n, _ck._dev_ptr(out_frames, "out_frames", torch.uint8, dev),
+            stride, st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+        with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+            macs = torch.as_strided(out_frames.reshape(-1), (n, hl), (stride, 1))[:, METADATA_LENGTH:].contiguous()
+    return out_frames, macs
+
+
+def package_batch_segments_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payloads,
+                                    frame_stride=None, ledger_id: int = 0):
+    """``package_batch_segments_host`` for MAC ledgers (bkd_digest_package_batch_segments_mac_host):
+    payloads[i] is a CompositeBuffer, a sequence of host buffers or one buffer; its leaves are hashed in
+    order without being joined on the CPU route and laid end to end in pinned staging on the GPU route.
+    Returns (headers uint8[n, frame_stride] = [32 B header][20 B MAC], macs uint8[n, 20])."""
+    leaves = [_leaves(p) for p in payloads]
+    n = len(leaves)
+    seg_first = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(l) for l in leaves], out=seg_first[1:])
+    views, ptrs, lens, first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
+    stride = frame_stride or (METADATA_LENGTH + MAC_LENGTH)
+    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
+    _keep, keys = _host_key_table_or(key_states, key_of, n)
+    frames = np.zeros((n, stride), dtype=np.uint8)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_package_batch_segments_mac_host(
+        *keys, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(first.ctypes.data), n,
+        vp(frames.ctypes.data), stride))
+    del views
+    return frames, frames[:, METADATA_LENGTH:METADATA_LENGTH + MAC_LENGTH].copy()
+
+
+def _host_key_table_or(key_states, key_of, count: int):
+    """``_host_key_table`` with an optional index: None is a null pointer (row 0 for every entry)."""
+    if key_of is not None:
+        return _host_key_table(key_states, key_of, "key_of", count)
+    table = np.ascontiguousarray(key_states, dtype=np.uint32)
+    if table.size % 10:
+        raise ValueError("key_states holds ten words per key (mac_key_table)")
+    return (table,), (ctypes.c_void_p(table.ctypes.data), table.size // 10, ctypes.c_void_p(0))
+
+
+def package_batch_v2_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
+                         master_key, *, key_stride=None, flags: int = FLAG_NONE,
+                         small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD, requests=None, request_offsets=None,
+                         align: int = 1, stream=None, sync_check: bool = False, ledger_id: int = 0,
+                         with_macs: bool = True):
+    """``package_batch_v2`` for MAC ledgers (bkd_digest_package_batch_v2_mac): request i is [int32 BE 76 + len]
+    [int32 BE packet header][20 B master key][32 B header][20 B MAC] and the payload behind it when it is
+    shorter than `small_threshold`, at request_offsets[i] of `requests` (``request_sizes_v2_mac``). The lane
+    that hashed an entry writes its 80-byte head; the copy pass is the CRC call's. Returns (requests,
+    request_offsets, macs uint8[n, 20], gathered from the requests that lie inside the buffer; None when
+    ``with_macs`` is false, which saves the gather)."""
+    import torch
+    n = offsets.numel()
+    dev = payload.device
+    i64, u32 = torch.int64, _ck._u32_dtypes()
+    keys, stride = _master_keys(master_key, n, key_stride, lambda a: torch.from_numpy(a.copy()).to(dev))
+    if request_offsets is None:
+        request_offsets, total = request_offsets_v2(request_sizes_v2_mac(lengths, small_threshold), align)
+        if requests is None:  # (the one host sync of this path: pass `requests` or offsets to avoid it)
+            requests = torch.empty(int(total) if n else 0, dtype=torch.uint8, device=dev)
+    elif requests is None:
+        raise ValueError("request_offsets given without the requests buffer they index")
+    with _ck._on_device(payload):
+        st = _ck._stream_ptr(stream, payload)
+        check(lib().bkd_digest_package_batch_v2_mac(
+            *_dev_key_table(key_states, key_of, "key_of", dev, n), ledger_id,
+            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
+            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
+            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
+            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
+            _ck._dev_ptr(keys, "master_key", torch.uint8, dev), stride, flags, small_threshold,
+            _ck._dev_ptr(requests, "requests", torch.uint8, dev), requests.numel(),
+            _ck._dev_ptr(request_offsets, "request_offsets", i64, dev, n), st))
+        if sync_check:
+            check(lib().bkd_stream_sync(st))
+        if not with_macs:
+            return requests, request_offsets, None
+        with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+            # the MAC bytes of every request whose head lies inside the buffer; zeros for the others
+            at = request_offsets.to(torch.int64) + (V2_PREFIX_LENGTH + METADATA_LENGTH)
+            inside = (at >= 0) & (at + MAC_LENGTH <= requests.numel())
+            idx = torch.where(inside, at, torch.zeros_like(at))[:, None] + torch.arange(MAC_LENGTH, device=dev)[None, :]
+            flat = requests.reshape(-1)
+            macs = flat[idx] * inside[:, None].to(torch.uint8) if flat.numel() >= MAC_LENGTH else \
+                torch.zeros((n, MAC_LENGTH), dtype=torch.uint8, device=dev)
+    return requests, request_offsets, macs
+
+
+def package_batch_v2_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key, *,
+                              key_stride=None, flags: int = FLAG_NONE,
+                              small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD, ledger_id: int = 0):
+    """``package_batch_v2_host`` for MAC ledgers (bkd_digest_package_batch_v2_mac_host): returns (the list of
+    request buffers, views of one allocation, macs uint8[n, 20])."""
+    views, ptrs, lens = _ck._host_entries(payloads)
+    n = len(views)
+    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
+    if not isinstance(master_key, (bytes, bytearray, memoryview)):
+        master_key = np.ascontiguousarray(master_key, dtype=np.uint8)
+    mkeys, stride = _master_keys(master_key, n, key_stride)
+    _keep, keys = _host_key_table_or(key_states, key_of, n)
+    offs, total = request_offsets_v2(request_sizes_v2_mac(lens, small_threshold))
+    buf = np.zeros(int(total) if n else 0, dtype=np.uint8)
+    rptr = (buf.ctypes.data + offs).astype(np.uint64)
+    vp = ctypes.c_void_p
+    check(lib().bkd_digest_package_batch_v2_mac_host(
+        *keys, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(mkeys.ctypes.data), stride, flags,
+        small_threshold, vp(rptr.ctypes.data)))
+    del views
+    ends = np.append(offs[1:], total) if n else offs
+    reqs = [buf[a:b] for a, b in zip(offs.tolist(), ends.tolist())]
+    head = V2_PREFIX_LENGTH + METADATA_LENGTH
+    macs = np.array([r[head:head + MAC_LENGTH] for r in reqs], dtype=np.uint8).reshape(n, MAC_LENGTH)
+    return reqs, macs
 
 
 class CRC32CDigestManager(DigestManager):
@@ -940,7 +1104,9 @@ class MacDigestManager(DigestManager):
     def _no_batch(self, *a, **k):
         raise NotImplementedError(
             "MAC ledgers have package_batch / verify_batch and their _host forms only: HMAC has no affine "
-            "shortcut, so a reframe is a full re-hash, and composite and V2 batches are not built for MAC")
+            "shortcut, so a reframe is a full re-hash; composite and V2 batches of MAC ledgers are the "
+            "module-level package_batch_segments_mac / package_batch_v2_mac and their _host forms, which "
+            "take a key table")
 
     reframe_batch = reframe_batch_host = _no_batch
     package_batch_segments = package_batch_segments_host = _no_batch

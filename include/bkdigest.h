@@ -566,6 +566,81 @@ BKD_API int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_stat
                                                       const uint32_t* h_lengths, uint64_t n, void* h_frames,
                                                       uint64_t frame_stride);
 
+/* MAC adds: composite payloads and V2 add requests, the two add-path shapes of a MAC ledger behind a
+ * Pulsar broker. Both span ledgers through the key table of bkd_digest_package_batch_ledgers_mac (one
+ * ledger: a table of one row): entry i is keyed with row d_key_of[i] and framed for d_ledger_ids[i];
+ * d_key_of == NULL keys every entry with row 0, d_ledger_ids == NULL frames every entry for ledger_id.
+ *
+ * An entry is unreadable when its key index is >= nkeys, when a non-empty segment (or its payload range)
+ * does not lie inside [0, payload_size), or when its length is over BKD_MAC_MAX_ENTRY. Its payload is not
+ * read; its 32-byte header is still written, with 20 zero MAC bytes, and the stream's bounds flag is
+ * raised (BKD_ERR_BOUNDS from the next bkd_stream_sync). Every load is an aligned dword that holds at
+ * least one byte of the segment it is loaded for, and no byte outside a segment's own bytes reaches the
+ * hash. Asynchronous on `stream`, no host synchronisation; n == 0 launches nothing.
+ *
+ * Segments: the segment arrays, the CSR d_seg_first and the frames exactly as in
+ * bkd_digest_package_batch_segments with a 20-byte digest (frame_stride >= 52, only 52 bytes of a stride
+ * written). Empty segments are skipped, wherever they say they lie; segments may be unaligned, overlap
+ * and be shared between entries; nseg == 0 with n > 0 is legal. A malformed d_seg_first is clamped as
+ * there (bkd_host_segments_range): the flag is raised and nothing outside the caller's arrays is read.
+ * HMAC has no algebra to join per-segment digests with, so one lane hashes its entry's segments as one
+ * byte stream, the SHA-1 blocks straddling the cuts; each payload byte is read once and none is copied.
+ * A composite entry's length is the 64-bit sum of its segments, given up as soon as it passes the cap
+ * (bkd_host_segments_length_capped), so no number of listings wraps to a short entry.
+ *
+ * V2: request i = [int32 BE 76 + len][int32 BE packet header][20 B master key][32 B header][20 B MAC]
+ * and the len payload bytes behind it when len < small_threshold, at d_requests + d_request_offsets[i]
+ * at any alignment; no other byte is written. key_stride (0 or >= 20), flags (16 bits) and
+ * small_threshold as in bkd_digest_package_batch_v2. An unreadable entry gets its 80-byte head and
+ * nothing is copied; a request whose range (the head, and the payload where it is copied) does not fit
+ * requests_size is not written at all and raises the flag. */
+BKD_API int bkd_digest_package_batch_segments_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                                  int64_t ledger_id, const int64_t* d_ledger_ids,
+                                                  const int64_t* d_entry_ids, const int64_t* d_lacs,
+                                                  const int64_t* d_length_fields, const void* d_payload,
+                                                  uint64_t payload_size, const uint64_t* d_seg_offsets,
+                                                  const uint32_t* d_seg_lengths, uint64_t nseg,
+                                                  const uint64_t* d_seg_first, uint64_t n, void* d_frames,
+                                                  uint64_t frame_stride, void* stream);
+BKD_API int bkd_digest_package_batch_v2_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
+                                            int64_t ledger_id, const int64_t* d_ledger_ids, const int64_t* d_entry_ids,
+                                            const int64_t* d_lacs, const int64_t* d_length_fields, const void* d_payload,
+                                            uint64_t payload_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                                            uint64_t n, const uint8_t* d_master_keys, uint64_t key_stride, uint32_t flags,
+                                            uint32_t small_threshold, void* d_requests, uint64_t requests_size,
+                                            const uint64_t* d_request_offsets, void* stream);
+/* Host-resident forms, shaped as bkd_digest_package_batch_segments_host / bkd_digest_package_batch_v2_host
+ * with the key table, nkeys and the index array (host memory; the index may be NULL) in front and no
+ * digest words out. Synchronous; the route as for the MAC host forms above. The index array (every value
+ * < nkeys) and the CSR (starts at 0, never decreases, ends at nseg) are checked before any work: a
+ * violation returns BKD_ERR_INVALID_ARG and writes nothing. CPU: the inner hash chained over an entry's
+ * non-empty segments, nothing joined; V2 copies a small payload right after hashing it. GPU: composite
+ * entries are laid end to end in pinned staging (an entry is never split between two staged segments)
+ * and go through bkd_digest_package_batch_ledgers_mac's device sequence; V2 is staged and packaged into
+ * 52-byte frames, and the host writes each prefix, key, header and MAC and copies the small payloads
+ * from their sources, so no payload byte comes back over PCIe. A batch that holds an entry over
+ * BKD_MAC_MAX_ENTRY takes the CPU route, or returns BKD_ERR_INVALID_ARG when the GPU is forced. */
+BKD_API int bkd_digest_package_batch_segments_mac_host(const uint32_t* h_key_states, uint64_t nkeys,
+                                                       const uint32_t* h_key_of, int64_t ledger_id,
+                                                       const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
+                                                       const int64_t* h_lacs, const int64_t* h_length_fields,
+                                                       const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths,
+                                                       uint64_t nseg, const uint64_t* h_seg_first, uint64_t n,
+                                                       void* h_frames, uint64_t frame_stride);
+BKD_API int bkd_digest_package_batch_v2_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
+                                                 int64_t ledger_id, const int64_t* h_ledger_ids,
+                                                 const int64_t* h_entry_ids, const int64_t* h_lacs,
+                                                 const int64_t* h_length_fields, const void* const* h_payloads,
+                                                 const uint32_t* h_lengths, uint64_t n, const uint8_t* h_master_keys,
+                                                 uint64_t key_stride, uint32_t flags, uint32_t small_threshold,
+                                                 void* const* h_requests);
+/* Host-only: the capped length of a composite MAC entry of segments h_seg_lengths[0, nseg): *bytes = their
+ * 64-bit sum where the summation stopped, which is as soon as it passed `cap`; returns 1 when it did (the
+ * entry is unreadable), else 0 (*bytes is the entry's length). The rule the device applies, for the CPU
+ * suite. */
+BKD_API int bkd_host_segments_length_capped(const uint32_t* h_seg_lengths, uint64_t nseg, uint64_t cap,
+                                            uint64_t* bytes);
+
 /* ---- synthetic input + test helpers --------------------------------------------------- */
 
 /* Fills nbytes of device memory with the little-endian splitmix64 stream
