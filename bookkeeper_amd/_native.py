@@ -126,6 +126,15 @@ PROTOTYPES = {
     "bkd_host_segments_length_capped": (_int, [_vp, _u64, _u64, _c.POINTER(_u64)]),
     "bkd_entrylog_index": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bkd_entrylog_verify": (_int, [_int, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_entrylog_verify_ledgers": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp,
+                                           _vp]),
+    "bkd_entrylog_verify_ledgers_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp,
+                                                _vp]),
+    "bkd_set_scrub_order": (_int, [_int]),
+    "bkd_get_scrub_order": (_int, []),
+    "bkd_get_scrub_host_route": (_int, [_vp, _u64, _u32]),
+    "bkd_host_scrub_bin": (_u32, [_u32]),
+    "bkd_host_scrub_lookup": (_i64, [_vp, _u64, _i64]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "bkd_host_tables": (_i64, [_int, _int, _vp, _u64]),
     "bkd_host_gf_mul": (_u32, [_int, _u32, _u32]),

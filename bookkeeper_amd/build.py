@@ -17,10 +17,11 @@ LIB = os.path.join(PKG, "libbkdigest.so")
 SOURCES = [os.path.join(CSRC, "bkdigest.hip")]
 # CPU route and host worker pool (plain C++, built with the host compiler)
 HOST_SOURCES = [os.path.join(CSRC, "host_crc.cpp"), os.path.join(CSRC, "host_batch.cpp"),
-                os.path.join(CSRC, "host_mac.cpp")]
+                os.path.join(CSRC, "host_mac.cpp"), os.path.join(CSRC, "host_scrub.cpp")]
 DEPS = SOURCES + HOST_SOURCES + [os.path.join(CSRC, f) for f in (
     "crc_kernels.hpp", "crc_tables.hpp", "plan_kernels.hpp", "host_crc.hpp", "host_batch.hpp",
-    "host_mac.hpp", "mac_kernels.hpp", "mac_segments.hpp", "mac_sha1.hpp")] + [os.path.join(ROOT, "include", "bkdigest.h")]
+    "host_mac.hpp", "mac_kernels.hpp", "mac_segments.hpp", "mac_sha1.hpp", "host_scrub.hpp", "scrub_kernels.hpp",
+    "scrub_rules.hpp")] + [os.path.join(ROOT, "include", "bkdigest.h")]
 ARCH = os.environ.get("BKD_OFFLOAD_ARCH", "gfx950")
 
 

@@ -31,7 +31,9 @@
 #include "host_batch.hpp"
 #include "host_crc.hpp"
 #include "host_mac.hpp"
+#include "host_scrub.hpp"
 #include "mac_kernels.hpp"
+#include "scrub_kernels.hpp"
 
 namespace {
 
@@ -67,8 +69,9 @@ int lane_index(int lanes) {
 // DESIGN.md §5a), so the library keeps no device memory of its own in that pool.
 struct StreamScratch {
     std::recursive_mutex mu;
-    static constexpr int kSlots = 4;
-    // slot 0: plan scratch (launch_plan), 1: verify pipeline, 2: segment CRCs, 3: package_v2's frames
+    static constexpr int kSlots = 5;
+    // slot 0: plan scratch (launch_plan), 1: verify pipeline, 2: segment CRCs, 3: package_v2's frames,
+    // 4: the ledger scrub's (its CRC classes nest the verify pipeline, which nests the plan)
     uint8_t* buf[kSlots] = {};
     size_t cap[kSlots] = {};
     // Sticky bounds-violation flag of the indexed batches enqueued on this stream (one per
@@ -1813,6 +1816,106 @@ int mac_host_route(const uint32_t* lengths, uint64_t n) {
     return 2;
 }
 
+// ---- the mixed-ledger entry-log scrub (scrub_kernels.hpp) -------------------------------------------
+
+std::atomic<int> g_scrub_order{0};  // bkd_set_scrub_order: 0 binned, 1 index order
+
+// The ledger table of bkd_entrylog_verify_ledgers and the key table its HMAC rows index.
+struct ScrubArgs {
+    const int64_t* ids;
+    const uint32_t* types;
+    const uint32_t* keys;
+    uint64_t nledgers;
+    const uint32_t* key_states;
+    uint64_t nkeys;
+    uint32_t mask;
+};
+
+// What every form of the call refuses before it looks for a device.
+int scrub_args_check(const void* log, const void* offsets, const void* lengths, uint64_t n, const ScrubArgs& a,
+                     const void* status, const void* first_bad) {
+    if (!first_bad) return fail(BKD_ERR_INVALID_ARG, "null first_bad");
+    if (n > 0 && (!log || !offsets || !lengths || !status)) return fail(BKD_ERR_INVALID_ARG, "null array");
+    if (n > 0xFFFFFFFFull) return fail(BKD_ERR_INVALID_ARG, "more than 2^32 - 1 entries");
+    if (a.nledgers > 0 && (!a.ids || !a.types)) return fail(BKD_ERR_INVALID_ARG, "null ledger table");
+    if (a.mask & ~bkd::scrub::kTypeMaskAll) return fail(BKD_ERR_INVALID_ARG, "types has bits above BKD_DIGEST_DUMMY");
+    if ((a.mask >> bkd::scrub::kHmac) & 1u) {
+        if (!a.key_states || a.nkeys == 0) return fail(BKD_ERR_INVALID_ARG, "the HMAC bit needs a key table");
+        if (a.nledgers > 0 && !a.keys) return fail(BKD_ERR_INVALID_ARG, "the HMAC bit needs the ledgers' key rows");
+    }
+    return BKD_OK;
+}
+
+// classify -> scan -> scatter -> one lane per HMAC frame -> verify_framed per CRC class in the mask ->
+// merge. All in stream order under the stream's lock; the HMAC count stays on the device (the grid of
+// mac_scrub_kernel is sized by n).
+int scrub_ledgers(DeviceState& ds, hipStream_t st, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                  const uint32_t* d_lengths, uint64_t n, const ScrubArgs& a, int32_t* d_status, uint64_t* d_first_bad) {
+    if (n == 0) {
+        BKD_HIP(hipMemsetAsync(d_first_bad, 0, sizeof(uint64_t), st));
+        return BKD_OK;
+    }
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    const bool has[2] = {((a.mask >> bkd::scrub::kCrc32c) & 1u) != 0, ((a.mask >> bkd::scrub::kCrc32) & 1u) != 0};
+    const bool has_mac = ((a.mask >> bkd::scrub::kHmac) & 1u) != 0;
+    Carver cv;
+    const size_t o_tag = cv.take(n * 4), o_krow = cv.take(has_mac ? n * 4 : 0), o_perm = cv.take(has_mac ? n * 4 : 0),
+                 o_counts = cv.take((bkd::scrub::kBins + 1) * 4);
+    size_t o_off[2], o_len[2], o_st[2], o_fb[2];
+    for (int c = 0; c < 2; ++c) {
+        o_off[c] = cv.take(has[c] ? n * 8 : 0);
+        o_len[c] = cv.take(has[c] ? n * 4 : 0);
+        o_st[c] = cv.take(has[c] ? n * 4 : 0);
+        o_fb[c] = cv.take(has[c] ? 8 : 0);
+    }
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);  // held across the nested verify sequences (slots 1 and 0)
+    uint8_t* sb = nullptr;
+    const hipError_t e = sc.get(4, cv.used, st, &sb);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("scrub scratch: ") + hipGetErrorString(e));
+    uint32_t* tag = Carver::at<uint32_t>(sb, o_tag);
+    uint32_t* krow = has_mac ? Carver::at<uint32_t>(sb, o_krow) : nullptr;
+    uint32_t* perm = has_mac ? Carver::at<uint32_t>(sb, o_perm) : nullptr;
+    uint32_t* counts = Carver::at<uint32_t>(sb, o_counts);
+    uint32_t* nmac = counts + bkd::scrub::kBins;
+    bkd::ScrubClass cls[2];
+    int32_t* cst[2];
+    for (int c = 0; c < 2; ++c) {
+        cls[c] = bkd::ScrubClass{has[c] ? Carver::at<uint64_t>(sb, o_off[c]) : nullptr,
+                                 has[c] ? Carver::at<uint32_t>(sb, o_len[c]) : nullptr};
+        cst[c] = has[c] ? Carver::at<int32_t>(sb, o_st[c]) : nullptr;
+    }
+    const int order = g_scrub_order.load(std::memory_order_relaxed);
+    const unsigned blocks = (unsigned)((n + bkd::kScrubBlock - 1) / bkd::kScrubBlock);
+    BKD_HIP(hipMemsetAsync(counts, 0, (bkd::scrub::kBins + 1) * 4, st));
+    const bkd::ScrubTable tab{a.ids, a.types, a.keys, a.nledgers, a.nkeys, a.mask};
+    hipLaunchKernelGGL(bkd::scrub_classify_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, (const uint8_t*)d_log,
+                       log_size, d_offsets, d_lengths, n, tab, cls[0], cls[1], tag, krow, counts, d_status, err);
+    BKD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkd::scrub_scan_kernel, dim3(1), dim3(1), 0, st, counts, nmac, n, order, d_first_bad);
+    BKD_HIP(hipGetLastError());
+    if (has_mac) {
+        hipLaunchKernelGGL(bkd::scrub_scatter_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, tag, n, order, counts,
+                           perm);
+        BKD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(bkd::mac_scrub_kernel, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, perm, nmac, tag, krow,
+                           a.key_states, a.nkeys, (const uint8_t*)d_log, d_offsets, d_lengths, n, d_status);
+        BKD_HIP(hipGetLastError());
+    }
+    for (int c = 0; c < 2; ++c) {
+        if (!has[c]) continue;
+        const int vr = verify_framed(ds, st, c, 0, 0, 2, d_log, log_size, cls[c].off, cls[c].len, n, cst[c],
+                                     Carver::at<uint64_t>(sb, o_fb[c]));
+        if (vr) return vr;
+    }
+    hipLaunchKernelGGL(bkd::scrub_merge_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, tag, cst[0], cst[1], n,
+                       d_status, (unsigned long long*)d_first_bad);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3085,6 +3188,127 @@ int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const ui
     Call call(stream);
     if (call.rc) return call.rc;
     return verify_framed(*call.ds, call.st, algo, 0, 0, 2, d_log, log_size, d_offsets, d_lengths, n, d_status, d_first_bad);
+}
+
+int bkd_entrylog_verify_ledgers(const void* d_log, uint64_t log_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                                uint64_t n, const int64_t* d_ledger_ids, const uint32_t* d_ledger_types,
+                                const uint32_t* d_ledger_keys, uint64_t nledgers, const uint32_t* d_key_states,
+                                uint64_t nkeys, uint32_t types, int32_t* d_status, uint64_t* d_first_bad, void* stream) {
+    const ScrubArgs a{d_ledger_ids, d_ledger_types, d_ledger_keys, nledgers, d_key_states, nkeys, types};
+    const int rc = scrub_args_check(d_log, d_offsets, d_lengths, n, a, d_status, d_first_bad);
+    if (rc) return rc;
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return scrub_ledgers(*call.ds, call.st, d_log, log_size, d_offsets, d_lengths, n, a, d_status, d_first_bad);
+}
+
+int bkd_entrylog_verify_ledgers_host(const void* h_log, uint64_t log_size, const uint64_t* h_offsets,
+                                     const uint32_t* h_lengths, uint64_t n, const int64_t* h_ledger_ids,
+                                     const uint32_t* h_ledger_types, const uint32_t* h_ledger_keys, uint64_t nledgers,
+                                     const uint32_t* h_key_states, uint64_t nkeys, uint32_t types, int32_t* h_status,
+                                     uint64_t* h_first_bad) {
+    const ScrubArgs a{h_ledger_ids, h_ledger_types, h_ledger_keys, nledgers, h_key_states, nkeys, types};
+    int rc = scrub_args_check(h_log, h_offsets, h_lengths, n, a, h_status, h_first_bad);
+    if (rc) return rc;
+    const bkd::host::ScrubLedgers t{h_ledger_ids, h_ledger_types, h_ledger_keys, nledgers, h_key_states, nkeys, types};
+    if (const uint64_t bad = bkd::host::scrub_table_check(t))
+        return fail(BKD_ERR_INVALID_ARG, "ledger table row " + std::to_string(bad - 1) +
+                                             ": ids must ascend strictly and an HMAC row's key index be < nkeys");
+    if (n == 0) {
+        *h_first_bad = 0;
+        return BKD_OK;
+    }
+    const int route = bkd_get_scrub_host_route(h_ledger_types, nledgers, types);
+    if (route == 1) {
+        const bool unreadable =
+            bkd::host::scrub_entries((const uint8_t*)h_log, log_size, h_offsets, h_lengths, n, t, h_status, h_first_bad);
+        return unreadable ? fail(BKD_ERR_BOUNDS, kBoundsMsg) : BKD_OK;
+    }
+    if (visible_devices() <= 0) return fail(BKD_ERR_NO_DEVICE, "no HIP device (host batch route forced to the GPU)");
+    // one upload into plain allocations on a stream of the call's own, so that its bounds flag is its own
+    struct Dev {
+        std::vector<void*> ptrs;
+        hipStream_t st = nullptr;
+        ~Dev() {
+            for (void* p : ptrs) (void)hipFree(p);
+            if (st) (void)hipStreamDestroy(st);
+        }
+        void* put(const void* h, size_t bytes) {  // nullptr on failure (or for nothing to copy)
+            if (!h || !bytes) return nullptr;
+            void* d = nullptr;
+            if (hipMalloc(&d, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                failed = true;
+                return nullptr;
+            }
+            ptrs.push_back(d);
+            if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) failed = true;
+            return d;
+        }
+        bool failed = false;
+    } dev;
+    BKD_HIP(hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking));
+    // the log rounded up to whole dwords: the last entry's last aligned dword lies inside the allocation
+    const size_t log_alloc = ((size_t)log_size + 3u) & ~(size_t)3u;
+    void* d_log = nullptr;
+    if (log_alloc) {
+        if (hipMalloc(&d_log, log_alloc) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BKD_ERR_NOMEM, "scrub: device allocation for the log failed");
+        }
+        dev.ptrs.push_back(d_log);
+        BKD_HIP(hipMemcpy(d_log, h_log, log_size, hipMemcpyHostToDevice));
+    }
+    const uint64_t* d_off = (const uint64_t*)dev.put(h_offsets, n * 8);
+    const uint32_t* d_len = (const uint32_t*)dev.put(h_lengths, n * 4);
+    const ScrubArgs da{(const int64_t*)dev.put(h_ledger_ids, nledgers * 8),
+                       (const uint32_t*)dev.put(h_ledger_types, nledgers * 4),
+                       (const uint32_t*)dev.put(h_ledger_keys, nledgers * 4),
+                       nledgers,
+                       (const uint32_t*)dev.put(h_key_states, nkeys * 40),
+                       nkeys,
+                       types};
+    std::vector<int32_t> none(n, 0);
+    int32_t* d_status = (int32_t*)dev.put(none.data(), n * 4);
+    uint64_t* d_fb = (uint64_t*)dev.put(&n, 8);
+    if (dev.failed) return fail(BKD_ERR_NOMEM, "scrub: device allocation or upload failed");
+    {
+        Call call((void*)dev.st);
+        if (call.rc) return call.rc;
+        rc = scrub_ledgers(*call.ds, call.st, d_log, log_size, d_off, d_len, n, da, d_status, d_fb);
+    }
+    // waits for the stream, frees its scratch and reports its bounds flag, whatever the launches answered
+    const int rel = bkd_stream_release((void*)dev.st);
+    if (rc) return rc;
+    if (rel && rel != BKD_ERR_BOUNDS) return rel;
+    BKD_HIP(hipMemcpy(h_status, d_status, n * 4, hipMemcpyDeviceToHost));
+    BKD_HIP(hipMemcpy(h_first_bad, d_fb, 8, hipMemcpyDeviceToHost));
+    return rel;
+}
+
+int bkd_set_scrub_order(int order) {
+    if (order != 0 && order != 1) return fail(BKD_ERR_INVALID_ARG, "scrub order is 0 (binned) or 1 (index order)");
+    g_scrub_order.store(order);
+    return BKD_OK;
+}
+
+int bkd_get_scrub_order(void) { return g_scrub_order.load(); }
+
+// automatic: the GPU only where the log has HMAC work for it; CRC stays on the host (§5)
+int bkd_get_scrub_host_route(const uint32_t* h_ledger_types, uint64_t nledgers, uint32_t types) {
+    const int r = g_host_route.load(std::memory_order_relaxed);
+    if (r != 0) return r;
+    bool mac = false;
+    if ((types >> bkd::scrub::kHmac) & 1u)
+        for (uint64_t k = 0; h_ledger_types && k < nledgers && !mac; ++k) mac = h_ledger_types[k] == bkd::scrub::kHmac;
+    return (mac && visible_devices() > 0) ? 2 : 1;
+}
+
+uint32_t bkd_host_scrub_bin(uint32_t frame_len) { return bkd::scrub::bin(frame_len); }
+
+int64_t bkd_host_scrub_lookup(const int64_t* ids, uint64_t nledgers, int64_t id) {
+    if (nledgers > 0 && !ids) return -1;
+    return bkd::scrub::lookup(ids, nledgers, id);
 }
 
 int bkd_crc_batch_segments(int algo, const void* d_base, uint64_t base_size, const uint64_t* d_seg_offsets,

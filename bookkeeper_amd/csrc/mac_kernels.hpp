@@ -11,7 +11,8 @@
 // The last partial block and the padding are built in registers (sha1::padded_word): bytes of the edge
 // dwords that lie outside the entry never reach the hash.
 //
-// Ragged batches: lanes whose entry is finished idle until the wave's longest entry ends.
+// Ragged batches: lanes whose entry is finished idle until the wave's longest entry ends (the entry-log
+// scrub bins its lanes by length instead, scrub_kernels.hpp).
 //
 // Keys and ids. The package and verify kernels are templates over a policy that supplies, per entry, the
 // key state and the ledger id (package) or the expected ids and the verified-prefix word (verify), as

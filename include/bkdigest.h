@@ -452,10 +452,81 @@ BKD_API int bkd_entrylog_index(const void* h_log, uint64_t log_size, uint64_t st
  * against the stored digest at 32) without ledger/entry id checks (the ledger id comes from the
  * entry itself). Status codes as bkd_digest_verify_batch (0 ok, 1 too short, 2 digest mismatch);
  * *d_first_bad = first failing index or n. One digest type per call (the ledger's, from its
- * metadata). Asynchronous on `stream`; ragged batches go through the chunked plan. */
+ * metadata; bkd_entrylog_verify_ledgers below takes a log that mixes types, MAC ledgers included).
+ * Asynchronous on `stream`; ragged batches go through the chunked plan. */
 BKD_API int bkd_entrylog_verify(int algo, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
                         const uint32_t* d_lengths, uint64_t n, int32_t* d_status, uint64_t* d_first_bad,
                         void* stream);
+
+/* Verify across ledgers and digest types: a whole entry-log index in one call. An entry log interleaves
+ * the entries of every ledger that was open while it was written; each ledger has its own digest type
+ * (DataFormats.proto:45-50) and a MAC ledger its own key. Entry i is d_log + d_offsets[i], d_lengths[i]
+ * bytes, as bkd_entrylog_index found it; its ledger id is its own first 8 bytes (big-endian), looked up in
+ * the ledger table d_ledger_ids[nledgers] (strictly ascending as signed values) by binary search. Row r has
+ * digest type d_ledger_types[r] (BKD_DIGEST_*) and, for HMAC, key row d_ledger_keys[r] of the nkeys x 10
+ * table bkd_mac_key_init fills (several ledgers may share a row). `types` is a mask of 1u << BKD_DIGEST_*:
+ * the types this call verifies; d_ledger_keys and d_key_states may be NULL when its HMAC bit is clear.
+ *
+ * d_status[i], with no ledger-id or entry-id checks:
+ *   offset + length > log_size: 1, not read, and the stream's bounds flag is raised (BKD_ERR_BOUNDS from
+ *     the next bkd_stream_sync); shorter than 8 bytes: 1;
+ *   ledger not in the table, a type value outside 0..3, or a type not in `types`: BKD_VERIFY_NOT_CHECKED;
+ *   CRC32C / CRC32: what bkd_entrylog_verify gives the entry (1 under 36 / 40 bytes, 2 digest mismatch);
+ *   HMAC: what bkd_digest_verify_batch_mac gives it without the id checks (1 under 52 bytes, 2 when any of
+ *     the 20 MAC bytes differs); longer than BKD_MAC_MAX_ENTRY or key row >= nkeys: not read, 1, and the
+ *     flag is raised; no word outside the key table is loaded;
+ *   DUMMY: 0 from 32 bytes on, else 1 (its digest is empty, DummyDigestManager.java:35-43,
+ *     DigestManager.java:229-235).
+ * *d_first_bad = the lowest index whose status is above 0, n when there is none. n == 0 writes 0 and
+ * launches nothing else; nledgers == 0 is legal (every readable entry of 8 bytes or more is
+ * BKD_VERIFY_NOT_CHECKED). n < 2^32. Asynchronous on `stream`, no host synchronisation.
+ *
+ * Device sequence (scrub_kernels.hpp): classify (one lane per entry) -> the HMAC frames
+ * counted into 73 length bins, four per power of two of their SHA-1 block count, and scattered bin by bin,
+ * longest first, so that the lanes of a wave hash entries of nearly one length (bkd_set_scrub_order) ->
+ * one lane per HMAC frame -> bkd_entrylog_verify's sequence once per CRC type in `types`, over the entries
+ * of that type -> merge. Every load of log bytes outside the CRC sequence is an aligned dword that holds a
+ * byte of the entry it is loaded for. The device does not validate the table's order: an unsorted table may
+ * make a listed ledger look unlisted, it never causes a load outside the three table arrays.
+ * Argument errors (a null array with n > 0 or nledgers > 0, `types` with bits above 3, the HMAC bit with a
+ * null key array or nkeys == 0, n >= 2^32) return BKD_ERR_INVALID_ARG before the device is looked for. */
+#define BKD_DIGEST_CRC32C 0 /* == BKD_CRC32C */
+#define BKD_DIGEST_CRC32 1  /* == BKD_CRC32 */
+#define BKD_DIGEST_HMAC 2
+#define BKD_DIGEST_DUMMY 3
+#define BKD_VERIFY_NOT_CHECKED (-1)
+BKD_API int bkd_entrylog_verify_ledgers(const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                                        const uint32_t* d_lengths, uint64_t n, const int64_t* d_ledger_ids,
+                                        const uint32_t* d_ledger_types, const uint32_t* d_ledger_keys,
+                                        uint64_t nledgers, const uint32_t* d_key_states, uint64_t nkeys,
+                                        uint32_t types, int32_t* d_status, uint64_t* d_first_bad, void* stream);
+/* Host-resident form: the log, the index, the tables and the outputs in host memory. Synchronous. The
+ * table's order and every HMAC row's key index (when the HMAC bit is in `types`) are checked before any
+ * work: a violation returns BKD_ERR_INVALID_ARG and writes nothing. Route (bkd_set_host_batch_route):
+ * 1 the CPU (the same lookup, DigestManager's arithmetic per entry on the host threads; no device needed),
+ * 2 the GPU (one upload of the log and the tables into plain allocations, the device call, the statuses
+ * copied back; BKD_ERR_NOMEM when an allocation fails), 0 automatic: the GPU when a device is visible and
+ * the table lists an HMAC ledger whose bit is in `types` (41.8 against 7.9 GB/s), else the
+ * CPU (the CRC crossover of DESIGN.md §5). Both routes write every status and *h_first_bad and then return
+ * BKD_ERR_BOUNDS when some entry was unreadable (out of range, over BKD_MAC_MAX_ENTRY, key row >= nkeys). */
+BKD_API int bkd_entrylog_verify_ledgers_host(const void* h_log, uint64_t log_size, const uint64_t* h_offsets,
+                                             const uint32_t* h_lengths, uint64_t n, const int64_t* h_ledger_ids,
+                                             const uint32_t* h_ledger_types, const uint32_t* h_ledger_keys,
+                                             uint64_t nledgers, const uint32_t* h_key_states, uint64_t nkeys,
+                                             uint32_t types, int32_t* h_status, uint64_t* h_first_bad);
+/* Which entries the HMAC lanes of bkd_entrylog_verify_ledgers take: 0 (default) binned by length, longest
+ * bin first; 1 index order, through the same kernels with an identity permutation. Results are identical;
+ * only the speed differs (tools/scrub_ab.py times both in one process). get: the current order. */
+BKD_API int bkd_set_scrub_order(int order);
+BKD_API int bkd_get_scrub_order(void);
+/* The route bkd_entrylog_verify_ledgers_host takes for this table and mask (1 the CPU, 2 the GPU): the
+ * forced route when one is set, else the automatic choice described above. */
+BKD_API int bkd_get_scrub_host_route(const uint32_t* h_ledger_types, uint64_t nledgers, uint32_t types);
+/* Host-only, for the CPU suite: the length bin of an HMAC frame of frame_len bytes (0..72; 0 under 52
+ * bytes, which are never hashed), and the row of `id` in the ascending table ids[0, nledgers) or -1 — the
+ * two rules the device applies (scrub_rules.hpp). */
+BKD_API uint32_t bkd_host_scrub_bin(uint32_t frame_len);
+BKD_API int64_t bkd_host_scrub_lookup(const int64_t* ids, uint64_t nledgers, int64_t id);
 
 /* ---- MAC ledgers: batched HMAC-SHA1 (DigestType.MAC, MacDigestManager) ------------------
  * MacDigestManager ($BK/proto/checksum/MacDigestManager.java:46-107) digests with HmacSHA1 keyed with
