@@ -1489,16 +1489,33 @@ struct HostSegments {
     }
 };
 
-// Null-pointer checks and the CSR of the host-resident composite calls, before any work: seg_first
-// starts at 0, never decreases and ends at nseg (BKD_ERR_INVALID_ARG otherwise).
+// The CSR of a host-resident call, before any work: `name` (req_first, seg_first) starts at 0, never
+// decreases over its `count` units (`noun`: a request, an entry) and ends at `total` (BKD_ERR_INVALID_ARG
+// otherwise); `count_name` and `total_name` are what the header calls the two.
+int check_csr(const char* name, const char* noun, const uint64_t* first, uint64_t count, const char* count_name,
+              uint64_t total, const char* total_name) {
+    if (first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, std::string(name) + "[0] is not 0");
+    for (uint64_t i = 0; i < count; ++i)
+        if (first[i + 1] < first[i])
+            return fail(BKD_ERR_INVALID_ARG, std::string(name) + " decreases at " + noun + " " + std::to_string(i));
+    if (first[count] != total)
+        return fail(BKD_ERR_INVALID_ARG, std::string(name) + "[" + count_name + "] is not " + total_name);
+    return BKD_OK;
+}
+
+// Every index names a row of a table of nkeys keys; `noun`: what an index belongs to (a request, an entry).
+int check_key_index(const char* noun, const uint32_t* index, uint64_t count, uint64_t nkeys) {
+    for (uint64_t i = 0; i < count; ++i)
+        if (index[i] >= nkeys)
+            return fail(BKD_ERR_INVALID_ARG, std::string(noun) + " " + std::to_string(i) + " names a key outside the table");
+    return BKD_OK;
+}
+
+// Null-pointer checks and the CSR of the host-resident composite calls, before any work.
 int check_host_segments(const void* const* h_seg_ptrs, const uint32_t* h_seg_lengths, uint64_t nseg,
                         const uint64_t* h_seg_first, uint64_t n) {
     if (!h_seg_first || (nseg && (!h_seg_ptrs || !h_seg_lengths))) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (h_seg_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "seg_first[0] is not 0");
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_seg_first[i + 1] < h_seg_first[i])
-            return fail(BKD_ERR_INVALID_ARG, "seg_first decreases at entry " + std::to_string(i));
-    if (h_seg_first[n] != nseg) return fail(BKD_ERR_INVALID_ARG, "seg_first[n] is not nseg");
+    if (int rc = check_csr("seg_first", "entry", h_seg_first, n, "n", nseg, "nseg")) return rc;
     for (uint64_t k = 0; k < nseg; ++k)
         if (h_seg_lengths[k] && !h_seg_ptrs[k]) return fail(BKD_ERR_INVALID_ARG, "null segment " + std::to_string(k));
     return BKD_OK;
@@ -1508,6 +1525,22 @@ int check_host_segments(const void* const* h_seg_ptrs, const uint32_t* h_seg_len
 int check_host_entries(const char* noun, const void* const* ptrs, const uint32_t* lens, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i)
         if (lens[i] && !ptrs[i]) return fail(BKD_ERR_INVALID_ARG, std::string("null ") + noun + " " + std::to_string(i));
+    return BKD_OK;
+}
+
+// The V2 forms' scalars, device- and host-resident, CRC and MAC: checked before n, so an empty batch too.
+int check_v2_args(uint64_t key_stride, uint32_t flags) {
+    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
+    return flags > 0xFFFFu ? fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits") : BKD_OK;
+}
+
+// The V2 host forms' entries: a payload as check_host_entries has it, and every entry a request buffer
+// (not check_host_entries: the first fault of either kind is the one named).
+int check_v2_entries(const void* const* payloads, const uint32_t* lens, void* const* requests, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
+        if (lens[i] && !payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
+        if (!requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
+    }
     return BKD_OK;
 }
 
@@ -1752,6 +1785,36 @@ struct DeviceTable {
     }
 };
 
+// The GPU route of the MAC package forms that take a key table (many ledgers, composite payloads, V2):
+// package_host_staged with the `stage` and `launch` they share. inner(hs, s, i0, cnt, bytes) stages the
+// entries (entry_buffers, HostSegments); each segment's key rows h_key_of[i0 ..] travel in the seeds buffer
+// beside them, and the table is uploaded once, by the first segment (the staged call has entered the device
+// by then). The device writes packed 52-byte frames and no digest words; `out` puts them where the form
+// wants them.
+template <class Inner, class Out>
+int mac_package_host_staged(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
+                            const int64_t* h_ledger_ids, const int64_t* h_entry_ids, const int64_t* h_lacs,
+                            const int64_t* h_length_fields, const Inner& inner, const uint32_t* h_lengths, uint64_t n,
+                            const Out& out) {
+    DeviceTable keys;
+    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        int r = keys.upload(h_key_states, nkeys);
+        if (r) return r;
+        r = inner(hs, s, i0, cnt, bytes);
+        if (r) return r;
+        memcpy(hs.h_seed[s], h_key_of + i0, cnt * 4);
+        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+        return BKD_OK;
+    };
+    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
+                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
+        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
+                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
+    };
+    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch,
+                               bkd::host::kMacFrameHead, false, out);
+}
+
 // Read requests of MAC ledgers (bkd_digest_verify_requests_mac; rq as verify_framed takes it, keys.index
 // per request): the CSR expanded into the stream's verify scratch and checked and the prefixes initialised
 // by request_expand_kernel, then the verify kernel over bkd::MacRequests.
@@ -1814,6 +1877,98 @@ int mac_host_route(const uint32_t* lengths, uint64_t n) {
                                                           " is longer than BKD_MAC_MAX_ENTRY (GPU route forced)")
                           : 1;
     return 2;
+}
+
+// One staged segment's expectations, as verify_requests_host has put them on the device: a ledger id, an
+// entry id and a flag word (bkd::host::kSkipEntryId or 0) per entry, then one zero u64 on an 8-byte boundary.
+// req_of: the host's request index | skip bit of the segment's entries.
+struct StagedRequests {
+    const int64_t *d_lid, *d_eid;
+    const uint32_t* d_flag;
+    const uint64_t* d_zero;
+    const uint32_t* req_of;
+};
+
+// bkd_digest_verify_requests_host and bkd_digest_verify_requests_mac_host. Checked before any work, in this
+// order: the request count, the request arrays, the MAC form's key table and per-request rows (`keys`; null
+// for CRC), the CSR, the entry buffers, each frame; a violation writes nothing. Then the requests become
+// per-entry expectations, which the CPU route checks frame by frame and the GPU route stages beside the
+// frames, and each request's verified prefix is its first non-zero status: the statuses come back to the
+// host on either route, so a request that straddles two staged segments gets the minimum over both parts.
+// host(xlid, xeid, req_of) returns the form's route (< 0: its error) and, where that is 1, has verified every
+// frame on the CPU. launch(ds, hs, s, cnt, bytes, x) enqueues the verify sequence over slot s's staged frames
+// and expectations x, statuses to d_res. init...: the StagedCall groups the launch needs.
+template <class Host, class Launch, class... Init>
+int verify_requests_host(const MacKeys* keys, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                         const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
+                         const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags, int32_t* h_status,
+                         uint64_t* h_req_first_bad, const Host& host, const Launch& launch, Init... init) {
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if ((keys && !keys->index) || !h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags ||
+        !h_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    if (keys && keys->nkeys && !keys->states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (keys)
+        if (int rc = check_key_index("request", keys->index, nreq, keys->nkeys)) return rc;
+    if (int rc = check_csr("req_first", "request", h_req_first, nreq, "nreq", n, "n")) return rc;
+    if (n && (!h_frames || !h_lengths || !h_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
+    for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
+    if (n == 0) return BKD_OK;
+    std::vector<int64_t> xlid(n), xeid(n);
+    std::vector<uint32_t> req_of(n);
+    for (uint64_t r = 0; r < nreq; ++r)
+        for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i) {
+            xlid[i] = h_req_ledger_ids[r];
+            xeid[i] = (int64_t)((uint64_t)h_req_first_entry_ids[r] + (i - h_req_first[r]));
+            req_of[i] = (uint32_t)r | ((h_req_flags[r] & 1u) ? bkd::host::kSkipEntryId : 0u);
+        }
+    auto prefixes = [&] {
+        for (uint64_t r = 0; r < nreq; ++r)
+            for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i)
+                if (h_status[i] != 0) {
+                    h_req_first_bad[r] = i - h_req_first[r];
+                    break;
+                }
+    };
+    const int route = host(xlid.data(), xeid.data(), req_of.data());
+    if (route < 0) return route;
+    if (route == 1) {
+        prefixes();
+        return BKD_OK;
+    }
+    StagedCall call(init...);
+    if (call.rc) return call.rc;
+    HostStage& hs = **call.lease;
+    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
+        const hipStream_t st = hs.st[s];
+        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
+        if (r) return r;
+        // [ledger ids][entry ids][flag words][pad to 8][one zero u64]
+        const size_t o_eid = cnt * 8, o_flag = cnt * 16, o_zero = (cnt * 20 + 7) & ~(size_t)7;
+        memcpy(hs.h_rq[s], xlid.data() + i0, cnt * 8);
+        memcpy(hs.h_rq[s] + o_eid, xeid.data() + i0, cnt * 8);
+        uint32_t* flag = reinterpret_cast<uint32_t*>(hs.h_rq[s] + o_flag);
+        for (uint64_t j = 0; j < cnt; ++j) flag[j] = req_of[i0 + j] & bkd::host::kSkipEntryId;
+        memset(hs.h_rq[s] + cnt * 20, 0, o_zero + 8 - cnt * 20);
+        BKD_HIP(hipMemcpyAsync(hs.d_rq[s], hs.h_rq[s], o_zero + 8, hipMemcpyHostToDevice, st));
+        const uint8_t* d = hs.d_rq[s];
+        r = launch(*call.ds, hs, s, cnt, bytes,
+                   StagedRequests{reinterpret_cast<const int64_t*>(d), reinterpret_cast<const int64_t*>(d + o_eid),
+                                  reinterpret_cast<const uint32_t*>(d + o_flag),
+                                  reinterpret_cast<const uint64_t*>(d + o_zero), req_of.data() + i0});
+        if (r) return r;
+        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
+        return BKD_OK;
+    };
+    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
+        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
+        return BKD_OK;
+    };
+    const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
+    if (rc == BKD_OK) prefixes();
+    return rc;
 }
 
 // ---- the mixed-ledger entry-log scrub (scrub_kernels.hpp) -------------------------------------------
@@ -2430,8 +2585,7 @@ int bkd_digest_package_batch_v2(int algo, int64_t ledger_id, const int64_t* d_le
                                 uint32_t small_threshold, void* d_requests, uint64_t requests_size,
                                 const uint64_t* d_request_offsets, uint32_t* d_digests, void* stream) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
-    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (int rc = check_v2_args(key_stride, flags)) return rc;
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_master_keys || !d_requests ||
         !d_request_offsets || !d_digests)
@@ -2450,16 +2604,12 @@ int bkd_digest_package_batch_v2_host(int algo, int64_t ledger_id, const int64_t*
                                      const uint8_t* h_master_keys, uint64_t key_stride, uint32_t flags,
                                      uint32_t small_threshold, void* const* h_requests, uint32_t* h_digests) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
-    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (int rc = check_v2_args(key_stride, flags)) return rc;
     if (n == 0) return BKD_OK;
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_master_keys || !h_requests ||
         !h_digests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    for (uint64_t i = 0; i < n; ++i) {  // (not check_host_entries: the first fault of either kind is the one named)
-        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
-        if (!h_requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
-    }
+    if (int rc = check_v2_entries(h_payloads, h_lengths, h_requests, n)) return rc;
     const int route = framed_host_route(h_lengths, n);
     if (route < 0) return route;
     const bkd::host::V2Head head{h_master_keys, key_stride, bkd::host::v2_packet_header(flags), small_threshold};
@@ -2487,81 +2637,26 @@ int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const
                                     const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags,
                                     int32_t* h_status, uint64_t* h_req_first_bad) {
     if (!valid_algo(algo)) return fail(BKD_ERR_INVALID_ARG, "unknown algorithm");
-    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
-    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
-    if (!h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags || !h_req_first_bad)
-        return fail(BKD_ERR_INVALID_ARG, "null request array");
-    // the CSR, before any work: starts at 0, never decreases, ends at n
-    if (h_req_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "req_first[0] is not 0");
-    for (uint64_t r = 0; r < nreq; ++r)
-        if (h_req_first[r + 1] < h_req_first[r])
-            return fail(BKD_ERR_INVALID_ARG, "req_first decreases at request " + std::to_string(r));
-    if (h_req_first[nreq] != n) return fail(BKD_ERR_INVALID_ARG, "req_first[nreq] is not n");
-    for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
-    if (n == 0) return BKD_OK;
-    if (!h_frames || !h_lengths || !h_status) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
-    const int route = framed_host_route(h_lengths, n);
-    if (route < 0) return route;
-    // the requests as per-entry expectations: what the CPU route checks frame by frame and what the
-    // GPU route stages beside the frames
-    std::vector<int64_t> xlid(n), xeid(n);
-    std::vector<uint32_t> req_of(n);
-    for (uint64_t r = 0; r < nreq; ++r)
-        for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i) {
-            xlid[i] = h_req_ledger_ids[r];
-            xeid[i] = (int64_t)((uint64_t)h_req_first_entry_ids[r] + (i - h_req_first[r]));
-            req_of[i] = (uint32_t)r | ((h_req_flags[r] & 1u) ? bkd::host::kSkipEntryId : 0u);
-        }
-    // statuses come back to the host on either route: each request's verified prefix is its first
-    // non-zero status
-    auto prefixes = [&] {
-        for (uint64_t r = 0; r < nreq; ++r)
-            for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i)
-                if (h_status[i] != 0) {
-                    h_req_first_bad[r] = i - h_req_first[r];
-                    break;
-                }
-    };
-    if (route == 1) {
-        bkd::host::verify_frames_expected(algo, xlid.data(), xeid.data(), req_of.data(), (const uint8_t* const*)h_frames,
-                                          h_lengths, n, h_status);
-        prefixes();
-        return BKD_OK;
-    }
-    StagedCall call(&HostStage::init_verify, &HostStage::init_requests);
-    if (call.rc) return call.rc;
-    HostStage& hs = **call.lease;
-    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        // [ledger ids][entry ids][request 0 + skip bit][pad to 8][one zero u64: request 0's first entry]
-        const size_t o_eid = cnt * 8, o_req = cnt * 16, o_zero = (cnt * 20 + 7) & ~(size_t)7;
-        memcpy(hs.h_rq[s], xlid.data() + i0, cnt * 8);
-        memcpy(hs.h_rq[s] + o_eid, xeid.data() + i0, cnt * 8);
-        uint32_t* rq_of = reinterpret_cast<uint32_t*>(hs.h_rq[s] + o_req);
-        for (uint64_t j = 0; j < cnt; ++j) rq_of[j] = req_of[i0 + j] & bkd::host::kSkipEntryId;
-        memset(hs.h_rq[s] + cnt * 20, 0, o_zero + 8 - cnt * 20);
-        BKD_HIP(hipMemcpyAsync(hs.d_rq[s], hs.h_rq[s], o_zero + 8, hipMemcpyHostToDevice, st));
-        const uint8_t* d = hs.d_rq[s];
-        Requests rq{1, reinterpret_cast<const uint64_t*>(d + o_zero), nullptr, nullptr, nullptr, hs.d_fb[s]};
-        rq.exp_lid = reinterpret_cast<const int64_t*>(d);
-        rq.exp_eid = reinterpret_cast<const int64_t*>(d + o_eid);
-        rq.req_of = reinterpret_cast<const uint32_t*>(d + o_req);
-        r = verify_framed(*call.ds, st, algo, 0, 0, 0, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
-                          reinterpret_cast<int32_t*>(hs.d_res[s]), nullptr, &rq);
-        if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
-        return BKD_OK;
-    };
-    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        return BKD_OK;
-    };
-    const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
-    if (rc == BKD_OK) prefixes();
-    return rc;
+    return verify_requests_host(
+        nullptr, h_frames, h_lengths, n, h_req_first, nreq, h_req_ledger_ids, h_req_first_entry_ids, h_req_flags, h_status,
+        h_req_first_bad,
+        [&](const int64_t* xlid, const int64_t* xeid, const uint32_t* req_of) {
+            const int route = framed_host_route(h_lengths, n);
+            if (route == 1)
+                bkd::host::verify_frames_expected(algo, xlid, xeid, req_of, (const uint8_t* const*)h_frames, h_lengths, n,
+                                                  h_status);
+            return route;
+        },
+        // every staged entry belongs to the segment's one request 0, which starts at its entry 0 (x.d_zero)
+        [&](DeviceState& ds, HostStage& hs, int s, uint64_t cnt, uint64_t bytes, const StagedRequests& x) {
+            Requests rq{1, x.d_zero, nullptr, nullptr, nullptr, hs.d_fb[s]};
+            rq.exp_lid = x.d_lid;
+            rq.exp_eid = x.d_eid;
+            rq.req_of = x.d_flag;
+            return verify_framed(ds, hs.st[s], algo, 0, 0, 0, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
+                                 reinterpret_cast<int32_t*>(hs.d_res[s]), nullptr, &rq);
+        },
+        &HostStage::init_verify, &HostStage::init_requests);
 }
 
 int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
@@ -2865,89 +2960,28 @@ int bkd_digest_verify_requests_mac_host(const uint32_t* h_key_states, uint64_t n
                                         const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
                                         const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags,
                                         int32_t* h_status, uint64_t* h_req_first_bad) {
-    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
-    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
-    if (!h_req_keys || !h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags || !h_req_first_bad)
-        return fail(BKD_ERR_INVALID_ARG, "null request array");
-    if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
-    // the key indices and the CSR, before any work: rows of the table; starts at 0, never decreases, ends at n
-    for (uint64_t r = 0; r < nreq; ++r)
-        if (h_req_keys[r] >= nkeys)
-            return fail(BKD_ERR_INVALID_ARG, "request " + std::to_string(r) + " names a key outside the table");
-    if (h_req_first[0] != 0u) return fail(BKD_ERR_INVALID_ARG, "req_first[0] is not 0");
-    for (uint64_t r = 0; r < nreq; ++r)
-        if (h_req_first[r + 1] < h_req_first[r])
-            return fail(BKD_ERR_INVALID_ARG, "req_first decreases at request " + std::to_string(r));
-    if (h_req_first[nreq] != n) return fail(BKD_ERR_INVALID_ARG, "req_first[nreq] is not n");
-    if (n && (!h_frames || !h_lengths || !h_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
-    if (int rc = check_host_entries("frame", h_frames, h_lengths, n)) return rc;
-    for (uint64_t r = 0; r < nreq; ++r) h_req_first_bad[r] = h_req_first[r + 1] - h_req_first[r];
-    if (n == 0) return BKD_OK;
-    const int route = mac_host_route(h_lengths, n);
-    if (route < 0) return route;
-    // the requests as per-entry expectations: what the CPU route checks frame by frame and what the GPU
-    // route stages beside the frames, with each entry's key row
-    std::vector<int64_t> xlid(n), xeid(n);
-    std::vector<uint32_t> req_of(n);
-    for (uint64_t r = 0; r < nreq; ++r)
-        for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i) {
-            xlid[i] = h_req_ledger_ids[r];
-            xeid[i] = (int64_t)((uint64_t)h_req_first_entry_ids[r] + (i - h_req_first[r]));
-            req_of[i] = (uint32_t)r | ((h_req_flags[r] & 1u) ? bkd::host::kSkipEntryId : 0u);
-        }
-    // the statuses come back to the host on either route, and a request's verified prefix is its first
-    // non-zero status: a request that straddles two staged segments gets the minimum over both parts
-    auto prefixes = [&] {
-        for (uint64_t r = 0; r < nreq; ++r)
-            for (uint64_t i = h_req_first[r]; i < h_req_first[r + 1]; ++i)
-                if (h_status[i] != 0) {
-                    h_req_first_bad[r] = i - h_req_first[r];
-                    break;
-                }
-    };
-    if (route == 1) {
-        bkd::host::mac_verify_frames_expected(h_key_states, h_req_keys, xlid.data(), xeid.data(), req_of.data(),
-                                              (const uint8_t* const*)h_frames, h_lengths, n, h_status);
-        prefixes();
-        return BKD_OK;
-    }
-    StagedCall call(&HostStage::init_requests);
-    if (call.rc) return call.rc;
-    HostStage& hs = **call.lease;
-    DeviceTable keys;  // uploaded once, before any segment is enqueued
-    if (int rc = keys.upload(h_key_states, nkeys)) return rc;
-    auto seg = [&](int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        const hipStream_t st = hs.st[s];
-        int r = stage_entries(hs, s, h_frames, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        // [ledger ids][entry ids][flag words] in the requests buffer, the key rows in the seeds buffer
-        const size_t o_eid = cnt * 8, o_flag = cnt * 16;
-        memcpy(hs.h_rq[s], xlid.data() + i0, cnt * 8);
-        memcpy(hs.h_rq[s] + o_eid, xeid.data() + i0, cnt * 8);
-        uint32_t* flag = reinterpret_cast<uint32_t*>(hs.h_rq[s] + o_flag);
-        for (uint64_t j = 0; j < cnt; ++j) {
-            flag[j] = req_of[i0 + j] & bkd::host::kSkipEntryId;
-            hs.h_seed[s][j] = h_req_keys[req_of[i0 + j] & ~bkd::host::kSkipEntryId];
-        }
-        BKD_HIP(hipMemcpyAsync(hs.d_rq[s], hs.h_rq[s], cnt * 20, hipMemcpyHostToDevice, st));
-        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, st));
-        const uint8_t* d = hs.d_rq[s];
-        const bkd::MacExpected who{keys.d, nkeys, hs.d_seed[s], reinterpret_cast<const int64_t*>(d),
-                                   reinterpret_cast<const int64_t*>(d + o_eid),
-                                   reinterpret_cast<const uint32_t*>(d + o_flag)};
-        r = mac_verify_expected(*call.ds, st, who, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
-                                reinterpret_cast<int32_t*>(hs.d_res[s]));
-        if (r) return r;
-        BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
-        return BKD_OK;
-    };
-    auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
-        memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        return BKD_OK;
-    };
-    const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
-    if (rc == BKD_OK) prefixes();
-    return rc;
+    const MacKeys keys{h_key_states, nkeys, h_req_keys};
+    DeviceTable table;  // uploaded once, by the first segment (the staged call has entered the device by then)
+    return verify_requests_host(
+        &keys, h_frames, h_lengths, n, h_req_first, nreq, h_req_ledger_ids, h_req_first_entry_ids, h_req_flags, h_status,
+        h_req_first_bad,
+        [&](const int64_t* xlid, const int64_t* xeid, const uint32_t* req_of) {
+            const int route = mac_host_route(h_lengths, n);
+            if (route == 1)
+                bkd::host::mac_verify_frames_expected(h_key_states, h_req_keys, xlid, xeid, req_of,
+                                                      (const uint8_t* const*)h_frames, h_lengths, n, h_status);
+            return route;
+        },
+        // each entry's key row travels in the seeds buffer
+        [&](DeviceState& ds, HostStage& hs, int s, uint64_t cnt, uint64_t bytes, const StagedRequests& x) -> int {
+            if (int rc = table.upload(h_key_states, nkeys)) return rc;
+            for (uint64_t j = 0; j < cnt; ++j) hs.h_seed[s][j] = h_req_keys[x.req_of[j] & ~bkd::host::kSkipEntryId];
+            BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
+            return mac_verify_expected(ds, hs.st[s], bkd::MacExpected{table.d, nkeys, hs.d_seed[s], x.d_lid, x.d_eid, x.d_flag},
+                                       hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
+                                       reinterpret_cast<int32_t*>(hs.d_res[s]));
+        },
+        &HostStage::init_requests);
 }
 
 int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
@@ -2962,9 +2996,7 @@ int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint
     if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
     constexpr uint64_t hl = bkd::host::kMacFrameHead;
     if (int rc = check_frame_stride(hl, frame_stride, true)) return rc;
-    for (uint64_t i = 0; i < n; ++i)  // before any work, so no frame is written
-        if (h_key_of[i] >= nkeys)
-            return fail(BKD_ERR_INVALID_ARG, "entry " + std::to_string(i) + " names a key outside the table");
+    if (int rc = check_key_index("entry", h_key_of, n, nkeys)) return rc;  // before any work: no frame is written
     if (int rc = check_host_entries("entry", h_payloads, h_lengths, n)) return rc;
     const int route = mac_host_route(h_lengths, n);
     if (route < 0) return route;
@@ -2974,25 +3006,9 @@ int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint
                                               (uint8_t*)h_frames, frame_stride);
         return BKD_OK;
     }
-    DeviceTable keys;  // uploaded once, by the first segment (the staged call has entered the device by then)
-    // each segment's key rows travel in the seeds buffer, beside the payloads
-    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        int r = keys.upload(h_key_states, nkeys);
-        if (r) return r;
-        r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        memcpy(hs.h_seed[s], h_key_of + i0, cnt * 4);
-        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
-        return BKD_OK;
-    };
-    // the device writes packed 52-byte frames and no digest words; the host puts each frame at its stride
-    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
-                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
-        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
-                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
-    };
-    return package_host_staged(h_ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch, hl, false,
-                               host_frames(hl, hl, h_frames, frame_stride, nullptr));
+    return mac_package_host_staged(h_key_states, nkeys, h_key_of, h_ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                                   entry_buffers(h_payloads, h_lengths), h_lengths, n,
+                                   host_frames(hl, hl, h_frames, frame_stride, nullptr));
 }
 
 int bkd_digest_package_batch_segments_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_key_of,
@@ -3023,8 +3039,7 @@ int bkd_digest_package_batch_v2_mac(const uint32_t* d_key_states, uint64_t nkeys
                                     uint64_t n, const uint8_t* d_master_keys, uint64_t key_stride, uint32_t flags,
                                     uint32_t small_threshold, void* d_requests, uint64_t requests_size,
                                     const uint64_t* d_request_offsets, void* stream) {
-    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
-    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (int rc = check_v2_args(key_stride, flags)) return rc;
     if (n == 0) return BKD_OK;
     if (!d_entry_ids || !d_lacs || !d_length_fields || !d_offsets || !d_lengths || !d_master_keys || !d_requests ||
         !d_request_offsets)
@@ -3052,10 +3067,8 @@ struct MacHostIds {
     int rc = BKD_OK;
     MacHostIds(uint64_t nkeys, const uint32_t* h_key_of, int64_t ledger_id, const int64_t* h_ledger_ids, uint64_t n)
         : key_of(h_key_of), ledger_ids(h_ledger_ids) {
-        if (!h_key_of && nkeys == 0) rc = fail(BKD_ERR_INVALID_ARG, "an empty key table");
-        for (uint64_t i = 0; h_key_of && i < n && !rc; ++i)
-            if (h_key_of[i] >= nkeys)
-                rc = fail(BKD_ERR_INVALID_ARG, "entry " + std::to_string(i) + " names a key outside the table");
+        if (h_key_of) rc = check_key_index("entry", h_key_of, n, nkeys);
+        else if (nkeys == 0) rc = fail(BKD_ERR_INVALID_ARG, "an empty key table");
     }
     // the GPU route's arrays, made only there
     void materialise(int64_t ledger_id, uint64_t n) {
@@ -3098,23 +3111,8 @@ int bkd_digest_package_batch_segments_mac_host(const uint32_t* h_key_states, uin
     // each entry's segments end to end in the staging buffer (HostSegments: an entry is never split between
     // two staged segments), then bkd_digest_package_batch_ledgers_mac's device sequence
     ids.materialise(ledger_id, n);
-    DeviceTable keys;  // uploaded once, by the first segment (the staged call has entered the device by then)
-    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        int r = keys.upload(h_key_states, nkeys);
-        if (r) return r;
-        r = segs(hs, s, i0, cnt, bytes);
-        if (r) return r;
-        memcpy(hs.h_seed[s], ids.key_of + i0, cnt * 4);
-        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
-        return BKD_OK;
-    };
-    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
-                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
-        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
-                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
-    };
-    return package_host_staged(ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, segs.entry_len.data(), n, launch,
-                               hl, false, host_frames(hl, hl, h_frames, frame_stride, nullptr));
+    return mac_package_host_staged(h_key_states, nkeys, ids.key_of, ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                                   segs, segs.entry_len.data(), n, host_frames(hl, hl, h_frames, frame_stride, nullptr));
 }
 
 int bkd_digest_package_batch_v2_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,
@@ -3123,16 +3121,12 @@ int bkd_digest_package_batch_v2_mac_host(const uint32_t* h_key_states, uint64_t 
                                          const void* const* h_payloads, const uint32_t* h_lengths, uint64_t n,
                                          const uint8_t* h_master_keys, uint64_t key_stride, uint32_t flags,
                                          uint32_t small_threshold, void* const* h_requests) {
-    if (key_stride != 0u && key_stride < 20u) return fail(BKD_ERR_INVALID_ARG, "key_stride must be 0 or at least 20");
-    if (flags > 0xFFFFu) return fail(BKD_ERR_INVALID_ARG, "flags must fit 16 bits");
+    if (int rc = check_v2_args(key_stride, flags)) return rc;
     if (n == 0) return BKD_OK;
     if (!h_entry_ids || !h_lacs || !h_length_fields || !h_payloads || !h_lengths || !h_master_keys || !h_requests)
         return fail(BKD_ERR_INVALID_ARG, "null buffer");
     if (nkeys && !h_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
-    for (uint64_t i = 0; i < n; ++i) {
-        if (h_lengths[i] && !h_payloads[i]) return fail(BKD_ERR_INVALID_ARG, "null payload " + std::to_string(i));
-        if (!h_requests[i]) return fail(BKD_ERR_INVALID_ARG, "null request " + std::to_string(i));
-    }
+    if (int rc = check_v2_entries(h_payloads, h_lengths, h_requests, n)) return rc;
     MacHostIds ids(nkeys, h_key_of, ledger_id, h_ledger_ids, n);  // before any work, so no request is written
     if (ids.rc) return ids.rc;
     const int route = mac_host_route(h_lengths, n);
@@ -3149,27 +3143,12 @@ int bkd_digest_package_batch_v2_mac_host(const uint32_t* h_key_states, uint64_t 
     // segment's frames go into the requests behind the prefix the host writes, the small payloads from their
     // sources
     ids.materialise(ledger_id, n);
-    DeviceTable keys;
-    auto stage = [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt, uint64_t bytes) -> int {
-        int r = keys.upload(h_key_states, nkeys);
-        if (r) return r;
-        r = stage_entries(hs, s, h_payloads, h_lengths, i0, cnt, bytes);
-        if (r) return r;
-        memcpy(hs.h_seed[s], ids.key_of + i0, cnt * 4);
-        BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, hs.st[s]));
-        return BKD_OK;
-    };
-    auto launch = [&](DeviceState& ds, HostStage& hs, int s, const int64_t* d_ids, const int64_t* d_ledger_ids,
-                      uint64_t cnt, uint64_t bytes, uint64_t stride) {
-        return mac_package(ds, hs.st[s], bkd::MacLedgers{keys.d, nkeys, hs.d_seed[s], d_ledger_ids}, d_ids, d_ids + cnt,
-                           d_ids + 2 * cnt, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_frm[s], stride);
-    };
-    constexpr uint64_t hl = bkd::host::kMacFrameHead;
-    return package_host_staged(ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields, stage, h_lengths, n, launch, hl, false,
-                               [&](const uint8_t* frm, const uint32_t*, uint64_t i0, uint64_t cnt) {
-                                   bkd::host::mac_finish_requests_v2(frm, payloads + i0, h_lengths + i0, cnt, head, i0,
-                                                                     requests + i0);
-                               });
+    return mac_package_host_staged(h_key_states, nkeys, ids.key_of, ids.ledger_ids, h_entry_ids, h_lacs, h_length_fields,
+                                   entry_buffers(h_payloads, h_lengths), h_lengths, n,
+                                   [&](const uint8_t* frm, const uint32_t*, uint64_t i0, uint64_t cnt) {
+                                       bkd::host::mac_finish_requests_v2(frm, payloads + i0, h_lengths + i0, cnt, head, i0,
+                                                                         requests + i0);
+                                   });
 }
 
 int bkd_host_segments_length_capped(const uint32_t* h_seg_lengths, uint64_t nseg, uint64_t cap, uint64_t* bytes) {

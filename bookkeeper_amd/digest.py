@@ -230,6 +230,12 @@ class DigestManager:
         """(the first C argument of those functions, what must stay alive while it is used)."""
         return self.algo, None
 
+    def _c_add_first(self):
+        """(algo, ledger id): what the composite and V2 package functions take in front."""
+        if self.algo is None:
+            raise NotImplementedError("DUMMY digests need no device work")
+        return self.algo, self.ledgerId
+
     # ---- batch device path (new) ----
     def package_batch(self, entry_ids, lacs, length_fields, payload, offsets, lengths, frame_stride=None,
                       stream=None, sync_check: bool = False):
@@ -310,8 +316,9 @@ class DigestManager:
         BKD_ERR_BOUNDS from the stream's next ``stream_sync`` (here, when ``sync_check``).
         Short and empty segments are legal anywhere, the payload's last byte and offset == size included:
         the device reads no byte outside a segment shorter than 16 bytes."""
-        return _package_segments(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payload, seg_offsets,
-                                 seg_lengths, seg_first, frame_stride, out_frames, stream, sync_check)
+        return _package_segments("bkd_digest_package_batch_segments", self._c_add_first(), self.macCodeLength, None,
+                                 entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths, seg_first, frame_stride,
+                                 out_frames, stream, sync_check)
 
     def package_batch_v2(self, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key, *,
                          key_stride=None, flags: int = FLAG_NONE, small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD,
@@ -329,9 +336,9 @@ class DigestManager:
         not written. Returns (requests, request_offsets, digests int32[n]). An out-of-range payload
         (digest 0, nothing copied) or a request outside ``requests`` (not written) raises BKD_ERR_BOUNDS
         from the stream's next ``stream_sync`` (here, when ``sync_check``)."""
-        return _package_v2(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payload, offsets, lengths,
-                           master_key, key_stride, flags, small_threshold, requests, request_offsets, align, stream,
-                           sync_check)
+        return _package_v2("bkd_digest_package_batch_v2", self._c_add_first(), self.macCodeLength, None, entry_ids, lacs,
+                           length_fields, payload, offsets, lengths, master_key, key_stride, flags, small_threshold,
+                           requests, request_offsets, align, stream, sync_check)
 
     # ---- batch host path (new; entries in host memory, SURVEY §8f rows 1-2 / BASELINE config 5) ----
     def package_batch_v2_host(self, entry_ids, lacs, length_fields, payloads, master_key, *, key_stride=None,
@@ -340,8 +347,8 @@ class DigestManager:
         list of uint8 arrays, request i whole — the bytes computeDigestAndPackageForSending returns with
         useV2Protocol for a small entry, its first 60 + mac bytes for a large one; digests uint32[n]).
         ``master_key``: 20 bytes for all, or n rows of uint8 keys."""
-        return _package_v2_host(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payloads, master_key,
-                                key_stride, flags, small_threshold)
+        return _package_v2_host("bkd_digest_package_batch_v2_host", self._c_add_first(), self.macCodeLength, None,
+                                entry_ids, lacs, length_fields, payloads, master_key, key_stride, flags, small_threshold)
 
     def verify_batch_host(self, frames, first_entry_id: int, skip_entry_check: bool = False):
         """BatchedReadOp.complete over a ByteBufList (BatchedReadOp.java:164-190): `frames` is a
@@ -371,8 +378,8 @@ class DigestManager:
         leaves as DigestManager.update chains it (DigestManager.java:62-72, 380-392); nothing is joined
         in Python; empty leaves may be passed anywhere.
         Returns (headers uint8[n, frame_stride] = [32 B header][digest], digests uint32[n])."""
-        return _package_segments_host(self.algo, self.ledgerId, None, entry_ids, lacs, length_fields, payloads,
-                                      frame_stride)
+        return _package_segments_host("bkd_digest_package_batch_segments_host", self._c_add_first(), self.macCodeLength,
+                                      None, entry_ids, lacs, length_fields, payloads, frame_stride)
 
     def reframe_batch_host(self, frames, first_entry_id: int, new_lacs, trusted: bool = False,
                            skip_entry_check: bool = False):
@@ -422,17 +429,12 @@ def _check_csr_sizes(nreq: int, *arrays) -> None:
                          "(req_first one more)")
 
 
-def verify_requests(digest_type, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags=None,
-                    stream=None):
-    """Verifies n framed device-resident entries grouped into read requests of different ledgers in one
-    launch sequence (bkd_digest_verify_requests). Request r owns entries [req_first[r], req_first[r+1])
-    (int64[nreq + 1], non-decreasing, from 0 to n; empty requests are legal), is read from ledger
-    ledger_ids[r] and expects entry ids first_entry_ids[r], first_entry_ids[r] + 1, ...; skip_flags[r]
-    bit 0 skips its entry-id check. Returns (status int32[n], req_first_bad int64[nreq]): request r's
-    entries [0, req_first_bad[r]) verified — BatchedReadOp's verified prefix per request. A malformed
-    req_first raises BKD_ERR_BOUNDS from the stream's next ``stream_sync``."""
+# The bodies below serve both digest families. `fn` is the library function, `first` its C arguments in front
+# of the per-entry arrays ((algo[, ledger id]) for CRC, ([ledger id]) for MAC), and `keys` the MAC forms' key
+# table, marshalled in front of those: (key_states, the index array, its name), None for CRC.
+
+def _verify_requests(fn, first, keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags, stream):
     import torch
-    algo = _algo_of(digest_type)
     n = offsets.numel()
     dev = framed.device
     i64, u32 = torch.int64, _ck._u32_dtypes()
@@ -446,14 +448,27 @@ def verify_requests(digest_type, framed, offsets, lengths, req_first, ledger_ids
     status = torch.empty(n, dtype=torch.int32, device=dev)
     req_first_bad = torch.empty(nreq, dtype=torch.int64, device=dev)
     with _ck._on_device(framed):
-        check(lib().bkd_digest_verify_requests(
-            algo, _ck._dev_ptr(framed, "framed"), framed.numel() * framed.element_size(),
-            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
-            _ck._dev_ptr(req_first, "req_first", i64, dev), nreq, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev),
-            _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev), _ck._dev_ptr(skip_flags, "skip_flags", u32, dev),
-            _ck._dev_ptr(status, "status"), _ck._dev_ptr(req_first_bad, "req_first_bad"),
-            _ck._stream_ptr(stream, framed)))
+        check(getattr(lib(), fn)(
+            *(_dev_key_table(*keys, dev, nreq) if keys else ()), *first, _ck._dev_ptr(framed, "framed"),
+            framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
+            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(req_first, "req_first", i64, dev), nreq,
+            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev), _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev),
+            _ck._dev_ptr(skip_flags, "skip_flags", u32, dev), _ck._dev_ptr(status, "status"),
+            _ck._dev_ptr(req_first_bad, "req_first_bad"), _ck._stream_ptr(stream, framed)))
     return status, req_first_bad
+
+
+def verify_requests(digest_type, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags=None,
+                    stream=None):
+    """Verifies n framed device-resident entries grouped into read requests of different ledgers in one
+    launch sequence (bkd_digest_verify_requests). Request r owns entries [req_first[r], req_first[r+1])
+    (int64[nreq + 1], non-decreasing, from 0 to n; empty requests are legal), is read from ledger
+    ledger_ids[r] and expects entry ids first_entry_ids[r], first_entry_ids[r] + 1, ...; skip_flags[r]
+    bit 0 skips its entry-id check. Returns (status int32[n], req_first_bad int64[nreq]): request r's
+    entries [0, req_first_bad[r]) verified — BatchedReadOp's verified prefix per request. A malformed
+    req_first raises BKD_ERR_BOUNDS from the stream's next ``stream_sync``."""
+    return _verify_requests("bkd_digest_verify_requests", (_algo_of(digest_type),), None, framed, offsets, lengths,
+                            req_first, ledger_ids, first_entry_ids, skip_flags, stream)
 
 
 def package_batch_ledgers(digest_type, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
@@ -465,29 +480,34 @@ def package_batch_ledgers(digest_type, ledger_ids, entry_ids, lacs, length_field
                            length_fields, payload, offsets, lengths, frame_stride, None, stream, sync_check)
 
 
-def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry_ids, skip_flags=None):
-    """``verify_requests`` for entries in host memory: `frames` is a sequence of host buffers, each one
-    framed entry; the request arrays are host sequences. A malformed req_first raises
-    BKD_ERR_INVALID_ARG before any work. Returns (status int32[n], req_first_bad uint64[nreq])."""
-    algo = _algo_of(digest_type)
+def _verify_requests_host(fn, first, keys, frames, req_first, ledger_ids, first_entry_ids, skip_flags):
     views, ptrs, lens = _ck._host_entries(frames)
     n = len(views)
-    first = np.ascontiguousarray(req_first, dtype=np.uint64)
-    if first.size < 1:
+    first_of = np.ascontiguousarray(req_first, dtype=np.uint64)
+    if first_of.size < 1:
         raise ValueError("req_first holds nreq + 1 values")
-    nreq = first.size - 1
+    nreq = first_of.size - 1
     lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
     eids = np.ascontiguousarray(first_entry_ids, dtype=np.int64)
     flags = np.zeros(nreq, dtype=np.uint32) if skip_flags is None else np.ascontiguousarray(skip_flags, dtype=np.uint32)
     _check_csr_sizes(nreq, lids.size, eids.size, flags.size)
+    _keep, table = _host_key_table(*keys, nreq) if keys else (None, ())
     status = np.zeros(n, dtype=np.int32)
     first_bad = np.zeros(nreq, dtype=np.uint64)
     vp = ctypes.c_void_p
-    check(lib().bkd_digest_verify_requests_host(
-        algo, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first.ctypes.data), nreq, vp(lids.ctypes.data),
+    check(getattr(lib(), fn)(
+        *table, *first, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first_of.ctypes.data), nreq, vp(lids.ctypes.data),
         vp(eids.ctypes.data), vp(flags.ctypes.data), vp(status.ctypes.data), vp(first_bad.ctypes.data)))
     del views
     return status, first_bad
+
+
+def verify_requests_host(digest_type, frames, req_first, ledger_ids, first_entry_ids, skip_flags=None):
+    """``verify_requests`` for entries in host memory: `frames` is a sequence of host buffers, each one
+    framed entry; the request arrays are host sequences. A malformed req_first raises
+    BKD_ERR_INVALID_ARG before any work. Returns (status int32[n], req_first_bad uint64[nreq])."""
+    return _verify_requests_host("bkd_digest_verify_requests_host", (_algo_of(digest_type),), None, frames, req_first,
+                                 ledger_ids, first_entry_ids, skip_flags)
 
 
 def package_batch_ledgers_host(digest_type, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride=None):
@@ -524,14 +544,16 @@ def _dev_key_table(key_states, index, name: str, dev, min_numel: int):
 
 
 def _host_key_table(key_states, index, name: str, count: int):
-    """(the table uint32[nkeys, 10] and the index uint32[count] to keep alive, then their C arguments)."""
+    """(the table uint32[nkeys, 10] and the index uint32[count] to keep alive, then their C arguments); an
+    index of None is a null pointer (row 0 for everything)."""
     table = np.ascontiguousarray(key_states, dtype=np.uint32)
     if table.size % 10:
         raise ValueError("key_states holds ten words per key (mac_key_table)")
-    idx = np.ascontiguousarray(index, dtype=np.uint32)
-    if idx.size != count:
+    idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint32)
+    if idx is not None and idx.size != count:
         raise ValueError(f"{name} has {idx.size} elements, needs {count}")
-    return (table, idx), (ctypes.c_void_p(table.ctypes.data), table.size // 10, ctypes.c_void_p(idx.ctypes.data))
+    return (table, idx), (ctypes.c_void_p(table.ctypes.data), table.size // 10,
+                          ctypes.c_void_p(0 if idx is None else idx.ctypes.data))
 
 
 def verify_requests_mac(key_states, req_keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids,
@@ -540,28 +562,8 @@ def verify_requests_mac(key_states, req_keys, framed, offsets, lengths, req_firs
     req_keys[r] (int32 / uint32 [nreq]) of key_states (a device tensor of ``mac_key_table``'s words). A key
     index outside the table gives its entries VERIFY_TOO_SHORT and, like a malformed req_first, raises
     BKD_ERR_BOUNDS from the stream's next ``stream_sync``. Returns (status int32[n], req_first_bad int64[nreq])."""
-    import torch
-    n = offsets.numel()
-    dev = framed.device
-    i64, u32 = torch.int64, _ck._u32_dtypes()
-    if req_first.numel() < 1:
-        raise ValueError("req_first holds nreq + 1 values")
-    nreq = req_first.numel() - 1
-    _check_csr_sizes(nreq, ledger_ids.numel(), first_entry_ids.numel(),
-                     None if skip_flags is None else skip_flags.numel())
-    if skip_flags is None:
-        skip_flags = torch.zeros(nreq, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    req_first_bad = torch.empty(nreq, dtype=torch.int64, device=dev)
-    with _ck._on_device(framed):
-        check(lib().bkd_digest_verify_requests_mac(
-            *_dev_key_table(key_states, req_keys, "req_keys", dev, nreq), _ck._dev_ptr(framed, "framed"),
-            framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
-            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(req_first, "req_first", i64, dev), nreq,
-            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev), _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev),
-            _ck._dev_ptr(skip_flags, "skip_flags", u32, dev), _ck._dev_ptr(status, "status"),
-            _ck._dev_ptr(req_first_bad, "req_first_bad"), _ck._stream_ptr(stream, framed)))
-    return status, req_first_bad
+    return _verify_requests("bkd_digest_verify_requests_mac", (), (key_states, req_keys, "req_keys"), framed, offsets,
+                            lengths, req_first, ledger_ids, first_entry_ids, skip_flags, stream)
 
 
 def package_batch_ledgers_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
@@ -586,25 +588,8 @@ def verify_requests_mac_host(key_states, req_keys, frames, req_first, ledger_ids
     """``verify_requests_host`` for MAC ledgers: key_states uint32[nkeys, 10] and req_keys[nreq] in host
     memory. A key index outside the table or a malformed req_first raises BKD_ERR_INVALID_ARG before any
     work. Returns (status int32[n], req_first_bad uint64[nreq])."""
-    views, ptrs, lens = _ck._host_entries(frames)
-    n = len(views)
-    first = np.ascontiguousarray(req_first, dtype=np.uint64)
-    if first.size < 1:
-        raise ValueError("req_first holds nreq + 1 values")
-    nreq = first.size - 1
-    lids = np.ascontiguousarray(ledger_ids, dtype=np.int64)
-    eids = np.ascontiguousarray(first_entry_ids, dtype=np.int64)
-    flags = np.zeros(nreq, dtype=np.uint32) if skip_flags is None else np.ascontiguousarray(skip_flags, dtype=np.uint32)
-    _check_csr_sizes(nreq, lids.size, eids.size, flags.size)
-    _keep, keys = _host_key_table(key_states, req_keys, "req_keys", nreq)
-    status = np.zeros(n, dtype=np.int32)
-    first_bad = np.zeros(nreq, dtype=np.uint64)
-    vp = ctypes.c_void_p
-    check(lib().bkd_digest_verify_requests_mac_host(
-        *keys, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first.ctypes.data), nreq, vp(lids.ctypes.data),
-        vp(eids.ctypes.data), vp(flags.ctypes.data), vp(status.ctypes.data), vp(first_bad.ctypes.data)))
-    del views
-    return status, first_bad
+    return _verify_requests_host("bkd_digest_verify_requests_mac_host", (), (key_states, req_keys, "req_keys"), frames,
+                                 req_first, ledger_ids, first_entry_ids, skip_flags)
 
 
 def package_batch_ledgers_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payloads,
@@ -620,35 +605,36 @@ def package_batch_ledgers_mac_host(key_states, key_of, ledger_ids, entry_ids, la
 
 # ---- composite payloads (a CompositeByteBuf add: DigestManager.java:62-72, 126-181, 380-392) ----
 
-def _package_segments(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths,
-                      seg_first, frame_stride, out_frames, stream, sync_check):
+def _package_segments(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths,
+                      seg_first, frame_stride, out_frames, stream, sync_check, keys=None, with_digests: bool = True):
+    """The device forms over composite payloads (`fn`, `first`, `keys`: above). Returns (frames, digests int32[n]
+    or None)."""
     import torch
-    if algo is None:
-        raise NotImplementedError("DUMMY digests need no device work")
     if seg_first.numel() < 1:
         raise ValueError("seg_first holds n + 1 values")
     n = seg_first.numel() - 1
     nseg = seg_offsets.numel()
     if seg_lengths.numel() != nseg:
         raise ValueError("seg_offsets/seg_lengths size mismatch")
-    hl = METADATA_LENGTH + _mac_of(algo)
+    hl = METADATA_LENGTH + mac
     stride = frame_stride or hl
     dev = payload.device
     if out_frames is None:
         out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
     elif stride >= hl and n and out_frames.numel() * out_frames.element_size() < (n - 1) * stride + hl:
         raise ValueError("out_frames is too small for n frames at this stride")
-    digests = torch.empty(n, dtype=torch.int32, device=dev)
+    digests = torch.empty(n, dtype=torch.int32, device=dev) if with_digests else None
     i64, u32 = torch.int64, _ck._u32_dtypes()
     with _ck._on_device(payload):
         st = _ck._stream_ptr(stream, payload)
-        check(lib().bkd_digest_package_batch_segments(
-            algo, ledger_id, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
+        check(getattr(lib(), fn)(
+            *(_dev_key_table(*keys, dev, n) if keys else ()), *first, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
             _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n), _ck._dev_ptr(lacs, "lacs", i64, dev, n),
             _ck._dev_ptr(length_fields, "length_fields", i64, dev, n), _ck._dev_ptr(payload, "payload"),
             payload.numel() * payload.element_size(), _ck._dev_ptr(seg_offsets, "seg_offsets", i64, dev),
             _ck._dev_ptr(seg_lengths, "seg_lengths", u32, dev), nseg, _ck._dev_ptr(seg_first, "seg_first", i64, dev), n,
-            _ck._dev_ptr(out_frames, "out_frames", torch.uint8, dev), stride, _ck._dev_ptr(digests, "digests"), st))
+            _ck._dev_ptr(out_frames, "out_frames", torch.uint8, dev), stride,
+            *((_ck._dev_ptr(digests, "digests"),) if with_digests else ()), st))
         if sync_check:
             check(lib().bkd_stream_sync(st))
     return out_frames, digests
@@ -660,8 +646,10 @@ def package_batch_segments(digest_type, ledger_ids, entry_ids, lacs, length_fiel
     aggregation queue's composite adds across ledgers in one launch sequence."""
     if ledger_ids is None:
         raise ValueError("ledger_ids holds one ledger id per entry")
-    return _package_segments(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payload, seg_offsets,
-                             seg_lengths, seg_first, frame_stride, out_frames, stream, sync_check)
+    algo = _algo_of(digest_type)
+    return _package_segments("bkd_digest_package_batch_segments", (algo, 0), _mac_of(algo), ledger_ids, entry_ids, lacs,
+                             length_fields, payload, seg_offsets, seg_lengths, seg_first, frame_stride, out_frames, stream,
+                             sync_check)
 
 
 def _leaves(payload) -> list:
@@ -676,23 +664,25 @@ def _leaves(payload) -> list:
     return [_ck._host_view(payload)]
 
 
-def _package_segments_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride):
-    if algo is None:
-        raise NotImplementedError("DUMMY digests need no device work")
+def _package_segments_host(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payloads, frame_stride, keys=None,
+                           with_digests: bool = True):
+    """The host forms over composite payloads (`fn`, `first`, `keys`: above). Returns (frames uint8[n,
+    frame_stride], digests uint32[n] or None)."""
     leaves = [_leaves(p) for p in payloads]
     n = len(leaves)
     seg_first = np.zeros(n + 1, dtype=np.uint64)
     np.cumsum([len(l) for l in leaves], out=seg_first[1:])
-    views, ptrs, lens, first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
-    stride = frame_stride or (METADATA_LENGTH + _mac_of(algo))
+    views, ptrs, lens, seg_first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
+    stride = frame_stride or (METADATA_LENGTH + mac)
     ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
+    _keep, table = _host_key_table(*keys, n) if keys else (None, ())
     frames = np.zeros((n, stride), dtype=np.uint8)
-    digests = np.zeros(n, dtype=np.uint32)
+    digests = np.zeros(n, dtype=np.uint32) if with_digests else None
     vp = ctypes.c_void_p
-    check(lib().bkd_digest_package_batch_segments_host(
-        algo, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
-        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(first.ctypes.data), n,
-        vp(frames.ctypes.data), stride, vp(digests.ctypes.data)))
+    check(getattr(lib(), fn)(
+        *table, *first, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(seg_first.ctypes.data), n,
+        vp(frames.ctypes.data), stride, *((vp(digests.ctypes.data),) if with_digests else ())))
     del views
     return frames, digests
 
@@ -701,8 +691,9 @@ def package_batch_segments_host(digest_type, ledger_ids, entry_ids, lacs, length
     """``DigestManager.package_batch_segments_host`` with ledger_ids[i] framing entry i."""
     if ledger_ids is None:
         raise ValueError("ledger_ids holds one ledger id per entry")
-    return _package_segments_host(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payloads,
-                                  frame_stride)
+    algo = _algo_of(digest_type)
+    return _package_segments_host("bkd_digest_package_batch_segments_host", (algo, 0), _mac_of(algo), ledger_ids,
+                                  entry_ids, lacs, length_fields, payloads, frame_stride)
 
 
 # ---- V2 add requests, packaged whole (DigestManager.java:126-167) ----
@@ -760,32 +751,35 @@ def _master_keys(master_key, n: int, key_stride, to_device=None):
     return master_key, stride
 
 
-def _package_v2(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key,
-                key_stride, flags, small_threshold, requests, request_offsets, align, stream, sync_check):
+def _package_v2(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths, master_key,
+                key_stride, flags, small_threshold, requests, request_offsets, align, stream, sync_check, keys=None,
+                with_digests: bool = True):
+    """The device forms that write V2 add requests (`fn`, `first`, `keys`: above). Returns (requests,
+    request_offsets, digests int32[n] or None)."""
     import torch
-    if algo is None:
-        raise NotImplementedError("DUMMY digests need no device work")
     n = offsets.numel()
     dev = payload.device
     i64, u32 = torch.int64, _ck._u32_dtypes()
-    keys, stride = _master_keys(master_key, n, key_stride, lambda a: torch.from_numpy(a.copy()).to(dev))
+    mkeys, stride = _master_keys(master_key, n, key_stride, lambda a: torch.from_numpy(a.copy()).to(dev))
     if request_offsets is None:
-        request_offsets, total = request_offsets_v2(request_sizes_v2(algo, lengths, small_threshold), align)
+        sizes = _request_sizes(V2_PREFIX_LENGTH + METADATA_LENGTH + mac, lengths, small_threshold)
+        request_offsets, total = request_offsets_v2(sizes, align)
         if requests is None:  # (the one host sync of this path: pass `requests` or offsets to avoid it)
             requests = torch.empty(int(total) if n else 0, dtype=torch.uint8, device=dev)
     elif requests is None:
         raise ValueError("request_offsets given without the requests buffer they index")
-    digests = torch.empty(n, dtype=torch.int32, device=dev)
+    digests = torch.empty(n, dtype=torch.int32, device=dev) if with_digests else None
     with _ck._on_device(payload):
         st = _ck._stream_ptr(stream, payload)
-        check(lib().bkd_digest_package_batch_v2(
-            algo, ledger_id, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
+        check(getattr(lib(), fn)(
+            *(_dev_key_table(*keys, dev, n) if keys else ()), *first, _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n),
             _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n), _ck._dev_ptr(lacs, "lacs", i64, dev, n),
             _ck._dev_ptr(length_fields, "length_fields", i64, dev, n), _ck._dev_ptr(payload, "payload"),
             payload.numel() * payload.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
-            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(keys, "master_key", torch.uint8, dev),
+            _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(mkeys, "master_key", torch.uint8, dev),
             stride, flags, small_threshold, _ck._dev_ptr(requests, "requests", torch.uint8, dev), requests.numel(),
-            _ck._dev_ptr(request_offsets, "request_offsets", i64, dev, n), _ck._dev_ptr(digests, "digests"), st))
+            _ck._dev_ptr(request_offsets, "request_offsets", i64, dev, n),
+            *((_ck._dev_ptr(digests, "digests"),) if with_digests else ()), st))
         if sync_check:
             check(lib().bkd_stream_sync(st))
     return requests, request_offsets, digests
@@ -797,30 +791,32 @@ def package_batch_v2(digest_type, ledger_ids, entry_ids, lacs, length_fields, pa
     """``DigestManager.package_batch_v2`` with ledger_ids[i] (int64[n]) framing entry i."""
     if ledger_ids is None:
         raise ValueError("ledger_ids holds one ledger id per entry")
-    return _package_v2(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
-                       master_key, key_stride, flags, small_threshold, requests, request_offsets, align, stream,
-                       sync_check)
+    algo = _algo_of(digest_type)
+    return _package_v2("bkd_digest_package_batch_v2", (algo, 0), _mac_of(algo), ledger_ids, entry_ids, lacs, length_fields,
+                       payload, offsets, lengths, master_key, key_stride, flags, small_threshold, requests,
+                       request_offsets, align, stream, sync_check)
 
 
-def _package_v2_host(algo, ledger_id, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key, key_stride,
-                     flags, small_threshold):
-    if algo is None:
-        raise NotImplementedError("DUMMY digests need no device work")
+def _package_v2_host(fn, first, mac, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key, key_stride, flags,
+                     small_threshold, keys=None, with_digests: bool = True):
+    """The host forms that write V2 add requests (`fn`, `first`, `keys`: above). Returns (the requests, views of
+    one allocation, digests uint32[n] or None)."""
     views, ptrs, lens = _ck._host_entries(payloads)
     n = len(views)
     ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
     if not isinstance(master_key, (bytes, bytearray, memoryview)):
         master_key = np.ascontiguousarray(master_key, dtype=np.uint8)
-    keys, stride = _master_keys(master_key, n, key_stride)
-    offs, total = request_offsets_v2(request_sizes_v2(algo, lens, small_threshold))
+    mkeys, stride = _master_keys(master_key, n, key_stride)
+    _keep, table = _host_key_table(*keys, n) if keys else (None, ())
+    offs, total = request_offsets_v2(_request_sizes(V2_PREFIX_LENGTH + METADATA_LENGTH + mac, lens, small_threshold))
     buf = np.zeros(int(total) if n else 0, dtype=np.uint8)
     rptr = (buf.ctypes.data + offs).astype(np.uint64)
-    digests = np.zeros(n, dtype=np.uint32)
+    digests = np.zeros(n, dtype=np.uint32) if with_digests else None
     vp = ctypes.c_void_p
-    check(lib().bkd_digest_package_batch_v2_host(
-        algo, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
-        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(keys.ctypes.data), stride, flags,
-        small_threshold, vp(rptr.ctypes.data), vp(digests.ctypes.data)))
+    check(getattr(lib(), fn)(
+        *table, *first, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
+        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(mkeys.ctypes.data), stride, flags,
+        small_threshold, vp(rptr.ctypes.data), *((vp(digests.ctypes.data),) if with_digests else ())))
     del views
     ends = np.append(offs[1:], total) if n else offs
     return [buf[a:b] for a, b in zip(offs.tolist(), ends.tolist())], digests
@@ -832,8 +828,9 @@ def package_batch_v2_host(digest_type, ledger_ids, entry_ids, lacs, length_field
     """``DigestManager.package_batch_v2_host`` with ledger_ids[i] framing entry i."""
     if ledger_ids is None:
         raise ValueError("ledger_ids holds one ledger id per entry")
-    return _package_v2_host(_algo_of(digest_type), 0, ledger_ids, entry_ids, lacs, length_fields, payloads, master_key,
-                            key_stride, flags, small_threshold)
+    algo = _algo_of(digest_type)
+    return _package_v2_host("bkd_digest_package_batch_v2_host", (algo, 0), _mac_of(algo), ledger_ids, entry_ids, lacs,
+                            length_fields, payloads, master_key, key_stride, flags, small_threshold)
 
 
 # ---- MAC adds: composite payloads and V2 add requests across ledgers ----
@@ -850,34 +847,14 @@ def package_batch_segments_mac(key_states, key_of, ledger_ids, entry_ids, lacs, 
     MAC_MAX_ENTRY bytes is not read: its header is written, its MAC bytes are zero, BKD_ERR_BOUNDS from the
     stream's next sync (here, when ``sync_check``)."""
     import torch
-    if seg_first.numel() < 1:
-        raise ValueError("seg_first holds n + 1 values")
-    n = seg_first.numel() - 1
-    nseg = seg_offsets.numel()
-    if seg_lengths.numel() != nseg:
-        raise ValueError("seg_offsets/seg_lengths size mismatch")
+    out_frames, _ = _package_segments("bkd_digest_package_batch_segments_mac", (ledger_id,), MAC_LENGTH, ledger_ids,
+                                      entry_ids, lacs, length_fields, payload, seg_offsets, seg_lengths, seg_first,
+                                      frame_stride, out_frames, stream, sync_check, (key_states, key_of, "key_of"), False)
     hl = METADATA_LENGTH + MAC_LENGTH
-    stride = frame_stride or hl
-    dev = payload.device
-    if out_frames is None:
-        out_frames = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-    elif stride >= hl and n and out_frames.numel() * out_frames.element_size() < (n - 1) * stride + hl:
-        raise ValueError("out_frames is too small for n frames at this stride")
-    i64, u32 = torch.int64, _ck._u32_dtypes()
     with _ck._on_device(payload):
-        st = _ck._stream_ptr(stream, payload)
-        check(lib().bkd_digest_package_batch_segments_mac(
-            *_dev_key_table(key_states, key_of, "key_of", dev, n), ledger_id,
-            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
-            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
-            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
-            _ck._dev_ptr(seg_offsets, "seg_offsets", i64, dev), _ck._dev_ptr(seg_lengths, "seg_lengths", u32, dev), nseg,
-            _ck._dev_ptr(seg_first, "seg_first", i64, dev), n, _ck._dev_ptr(out_frames, "out_frames", torch.uint8, dev),
-            stride, st))
-        if sync_check:
-            check(lib().bkd_stream_sync(st))
         with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
-            macs = torch.as_strided(out_frames.reshape(-1), (n, hl), (stride, 1))[:, METADATA_LENGTH:].contiguous()
+            macs = torch.as_strided(out_frames.reshape(-1), (seg_first.numel() - 1, hl),
+                                    (frame_stride or hl, 1))[:, METADATA_LENGTH:].contiguous()
     return out_frames, macs
 
 
@@ -887,32 +864,10 @@ def package_batch_segments_mac_host(key_states, key_of, ledger_ids, entry_ids, l
     payloads[i] is a CompositeBuffer, a sequence of host buffers or one buffer; its leaves are hashed in
     order without being joined on the CPU route and laid end to end in pinned staging on the GPU route.
     Returns (headers uint8[n, frame_stride] = [32 B header][20 B MAC], macs uint8[n, 20])."""
-    leaves = [_leaves(p) for p in payloads]
-    n = len(leaves)
-    seg_first = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(l) for l in leaves], out=seg_first[1:])
-    views, ptrs, lens, first, _ = _ck._host_segments([v for l in leaves for v in l], seg_first)
-    stride = frame_stride or (METADATA_LENGTH + MAC_LENGTH)
-    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
-    _keep, keys = _host_key_table_or(key_states, key_of, n)
-    frames = np.zeros((n, stride), dtype=np.uint8)
-    vp = ctypes.c_void_p
-    check(lib().bkd_digest_package_batch_segments_mac_host(
-        *keys, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
-        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), len(views), vp(first.ctypes.data), n,
-        vp(frames.ctypes.data), stride))
-    del views
+    frames, _ = _package_segments_host("bkd_digest_package_batch_segments_mac_host", (ledger_id,), MAC_LENGTH, ledger_ids,
+                                       entry_ids, lacs, length_fields, payloads, frame_stride,
+                                       (key_states, key_of, "key_of"), False)
     return frames, frames[:, METADATA_LENGTH:METADATA_LENGTH + MAC_LENGTH].copy()
-
-
-def _host_key_table_or(key_states, key_of, count: int):
-    """``_host_key_table`` with an optional index: None is a null pointer (row 0 for every entry)."""
-    if key_of is not None:
-        return _host_key_table(key_states, key_of, "key_of", count)
-    table = np.ascontiguousarray(key_states, dtype=np.uint32)
-    if table.size % 10:
-        raise ValueError("key_states holds ten words per key (mac_key_table)")
-    return (table,), (ctypes.c_void_p(table.ctypes.data), table.size // 10, ctypes.c_void_p(0))
 
 
 def package_batch_v2_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payload, offsets, lengths,
@@ -927,31 +882,14 @@ def package_batch_v2_mac(key_states, key_of, ledger_ids, entry_ids, lacs, length
     request_offsets, macs uint8[n, 20], gathered from the requests that lie inside the buffer; None when
     ``with_macs`` is false, which saves the gather)."""
     import torch
-    n = offsets.numel()
-    dev = payload.device
-    i64, u32 = torch.int64, _ck._u32_dtypes()
-    keys, stride = _master_keys(master_key, n, key_stride, lambda a: torch.from_numpy(a.copy()).to(dev))
-    if request_offsets is None:
-        request_offsets, total = request_offsets_v2(request_sizes_v2_mac(lengths, small_threshold), align)
-        if requests is None:  # (the one host sync of this path: pass `requests` or offsets to avoid it)
-            requests = torch.empty(int(total) if n else 0, dtype=torch.uint8, device=dev)
-    elif requests is None:
-        raise ValueError("request_offsets given without the requests buffer they index")
+    requests, request_offsets, _ = _package_v2(
+        "bkd_digest_package_batch_v2_mac", (ledger_id,), MAC_LENGTH, ledger_ids, entry_ids, lacs, length_fields, payload,
+        offsets, lengths, master_key, key_stride, flags, small_threshold, requests, request_offsets, align, stream,
+        sync_check, (key_states, key_of, "key_of"), False)
+    if not with_macs:
+        return requests, request_offsets, None
+    n, dev = offsets.numel(), payload.device
     with _ck._on_device(payload):
-        st = _ck._stream_ptr(stream, payload)
-        check(lib().bkd_digest_package_batch_v2_mac(
-            *_dev_key_table(key_states, key_of, "key_of", dev, n), ledger_id,
-            _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev, n), _ck._dev_ptr(entry_ids, "entry_ids", i64, dev, n),
-            _ck._dev_ptr(lacs, "lacs", i64, dev, n), _ck._dev_ptr(length_fields, "length_fields", i64, dev, n),
-            _ck._dev_ptr(payload, "payload"), payload.numel() * payload.element_size(),
-            _ck._dev_ptr(offsets, "offsets", i64, dev), _ck._dev_ptr(lengths, "lengths", u32, dev, n), n,
-            _ck._dev_ptr(keys, "master_key", torch.uint8, dev), stride, flags, small_threshold,
-            _ck._dev_ptr(requests, "requests", torch.uint8, dev), requests.numel(),
-            _ck._dev_ptr(request_offsets, "request_offsets", i64, dev, n), st))
-        if sync_check:
-            check(lib().bkd_stream_sync(st))
-        if not with_macs:
-            return requests, request_offsets, None
         with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
             # the MAC bytes of every request whose head lies inside the buffer; zeros for the others
             at = request_offsets.to(torch.int64) + (V2_PREFIX_LENGTH + METADATA_LENGTH)
@@ -968,26 +906,11 @@ def package_batch_v2_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, l
                               small_threshold: int = SMALL_ENTRY_SIZE_THRESHOLD, ledger_id: int = 0):
     """``package_batch_v2_host`` for MAC ledgers (bkd_digest_package_batch_v2_mac_host): returns (the list of
     request buffers, views of one allocation, macs uint8[n, 20])."""
-    views, ptrs, lens = _ck._host_entries(payloads)
-    n = len(views)
-    ids, lac, lf, lids = _entry_fields(n, entry_ids, lacs, length_fields, ledger_ids, optional_ledgers=True)
-    if not isinstance(master_key, (bytes, bytearray, memoryview)):
-        master_key = np.ascontiguousarray(master_key, dtype=np.uint8)
-    mkeys, stride = _master_keys(master_key, n, key_stride)
-    _keep, keys = _host_key_table_or(key_states, key_of, n)
-    offs, total = request_offsets_v2(request_sizes_v2_mac(lens, small_threshold))
-    buf = np.zeros(int(total) if n else 0, dtype=np.uint8)
-    rptr = (buf.ctypes.data + offs).astype(np.uint64)
-    vp = ctypes.c_void_p
-    check(lib().bkd_digest_package_batch_v2_mac_host(
-        *keys, ledger_id, vp(0 if lids is None else lids.ctypes.data), vp(ids.ctypes.data), vp(lac.ctypes.data),
-        vp(lf.ctypes.data), vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(mkeys.ctypes.data), stride, flags,
-        small_threshold, vp(rptr.ctypes.data)))
-    del views
-    ends = np.append(offs[1:], total) if n else offs
-    reqs = [buf[a:b] for a, b in zip(offs.tolist(), ends.tolist())]
+    reqs, _ = _package_v2_host("bkd_digest_package_batch_v2_mac_host", (ledger_id,), MAC_LENGTH, ledger_ids, entry_ids,
+                               lacs, length_fields, payloads, master_key, key_stride, flags, small_threshold,
+                               (key_states, key_of, "key_of"), False)
     head = V2_PREFIX_LENGTH + METADATA_LENGTH
-    macs = np.array([r[head:head + MAC_LENGTH] for r in reqs], dtype=np.uint8).reshape(n, MAC_LENGTH)
+    macs = np.array([r[head:head + MAC_LENGTH] for r in reqs], dtype=np.uint8).reshape(len(reqs), MAC_LENGTH)
     return reqs, macs
 
 
