@@ -2001,6 +2001,73 @@ int scrub_args_check(const void* log, const void* offsets, const void* lengths, 
     return BKD_OK;
 }
 
+// The scrub's carve of the stream's scratch slot 4: what classify, scan and scatter write, then one set of
+// arrays per CRC class in the mask. `own_outputs` adds a status array and a first_bad word for a caller that
+// has none of its own (bkd_entrylog_scrub_lanes).
+struct ScrubCarve {
+    bool has[2], has_mac;
+    size_t o_tag, o_krow, o_perm, o_counts, o_off[2], o_len[2], o_st[2], o_fb[2], o_status, o_first, used;
+    uint32_t *tag, *krow, *perm, *counts, *nmac;
+    bkd::ScrubClass cls[2];
+    int32_t* cst[2];
+
+    ScrubCarve(uint64_t n, uint32_t mask, bool own_outputs) {
+        has[0] = ((mask >> bkd::scrub::kCrc32c) & 1u) != 0;
+        has[1] = ((mask >> bkd::scrub::kCrc32) & 1u) != 0;
+        has_mac = ((mask >> bkd::scrub::kHmac) & 1u) != 0;
+        Carver cv;
+        o_tag = cv.take(n * 4);
+        o_krow = cv.take(has_mac ? n * 4 : 0);
+        o_perm = cv.take(has_mac ? n * 4 : 0);
+        o_counts = cv.take((bkd::scrub::kBins + 1) * 4);
+        for (int c = 0; c < 2; ++c) {
+            o_off[c] = cv.take(has[c] ? n * 8 : 0);
+            o_len[c] = cv.take(has[c] ? n * 4 : 0);
+            o_st[c] = cv.take(has[c] ? n * 4 : 0);
+            o_fb[c] = cv.take(has[c] ? 8 : 0);
+        }
+        o_status = cv.take(own_outputs ? n * 4 : 0);
+        o_first = cv.take(own_outputs ? 8 : 0);
+        used = cv.used;
+    }
+    void bind(uint8_t* sb) {
+        tag = Carver::at<uint32_t>(sb, o_tag);
+        krow = has_mac ? Carver::at<uint32_t>(sb, o_krow) : nullptr;
+        perm = has_mac ? Carver::at<uint32_t>(sb, o_perm) : nullptr;
+        counts = Carver::at<uint32_t>(sb, o_counts);
+        nmac = counts + bkd::scrub::kBins;
+        for (int c = 0; c < 2; ++c) {
+            cls[c] = bkd::ScrubClass{has[c] ? Carver::at<uint64_t>(sb, o_off[c]) : nullptr,
+                                     has[c] ? Carver::at<uint32_t>(sb, o_len[c]) : nullptr};
+            cst[c] = has[c] ? Carver::at<int32_t>(sb, o_st[c]) : nullptr;
+        }
+    }
+};
+
+// classify -> scan -> scatter in stream order: every entry's tag (and final status where it has one), the
+// HMAC frames' lanes in cv.perm[0, *cv.nmac) in the order bkd_set_scrub_order asks for, *d_first_bad = n.
+// Shared by the full call and bkd_entrylog_scrub_lanes.
+int scrub_order_lanes(hipStream_t st, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                      const uint32_t* d_lengths, uint64_t n, const ScrubArgs& a, const ScrubCarve& cv, uint32_t* err,
+                      int32_t* d_status, uint64_t* d_first_bad) {
+    const int order = g_scrub_order.load(std::memory_order_relaxed);
+    const unsigned blocks = (unsigned)((n + bkd::kScrubBlock - 1) / bkd::kScrubBlock);
+    BKD_HIP(hipMemsetAsync(cv.counts, 0, (bkd::scrub::kBins + 1) * 4, st));
+    const bkd::ScrubTable tab{a.ids, a.types, a.keys, a.nledgers, a.nkeys, a.mask};
+    hipLaunchKernelGGL(bkd::scrub_classify_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, (const uint8_t*)d_log,
+                       log_size, d_offsets, d_lengths, n, tab, cv.cls[0], cv.cls[1], cv.tag, cv.krow, cv.counts, d_status,
+                       err);
+    BKD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkd::scrub_scan_kernel, dim3(1), dim3(1), 0, st, cv.counts, cv.nmac, n, order, d_first_bad);
+    BKD_HIP(hipGetLastError());
+    if (cv.has_mac) {
+        hipLaunchKernelGGL(bkd::scrub_scatter_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, cv.tag, n, order,
+                           cv.counts, cv.perm);
+        BKD_HIP(hipGetLastError());
+    }
+    return BKD_OK;
+}
+
 // classify -> scan -> scatter -> one lane per HMAC frame -> verify_framed per CRC class in the mask ->
 // merge. All in stream order under the stream's lock; the HMAC count stays on the device (the grid of
 // mac_scrub_kernel is sized by n).
@@ -2011,63 +2078,58 @@ int scrub_ledgers(DeviceState& ds, hipStream_t st, const void* d_log, uint64_t l
         return BKD_OK;
     }
     uint32_t* err = nullptr;
-    const int rc = bounds_flag(ds, st, &err);
+    int rc = bounds_flag(ds, st, &err);
     if (rc) return rc;
-    const bool has[2] = {((a.mask >> bkd::scrub::kCrc32c) & 1u) != 0, ((a.mask >> bkd::scrub::kCrc32) & 1u) != 0};
-    const bool has_mac = ((a.mask >> bkd::scrub::kHmac) & 1u) != 0;
-    Carver cv;
-    const size_t o_tag = cv.take(n * 4), o_krow = cv.take(has_mac ? n * 4 : 0), o_perm = cv.take(has_mac ? n * 4 : 0),
-                 o_counts = cv.take((bkd::scrub::kBins + 1) * 4);
-    size_t o_off[2], o_len[2], o_st[2], o_fb[2];
-    for (int c = 0; c < 2; ++c) {
-        o_off[c] = cv.take(has[c] ? n * 8 : 0);
-        o_len[c] = cv.take(has[c] ? n * 4 : 0);
-        o_st[c] = cv.take(has[c] ? n * 4 : 0);
-        o_fb[c] = cv.take(has[c] ? 8 : 0);
-    }
+    ScrubCarve cv(n, a.mask, false);
     StreamScratch& sc = scratch_for(ds, st);
     std::lock_guard<std::recursive_mutex> lk(sc.mu);  // held across the nested verify sequences (slots 1 and 0)
     uint8_t* sb = nullptr;
     const hipError_t e = sc.get(4, cv.used, st, &sb);
     if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("scrub scratch: ") + hipGetErrorString(e));
-    uint32_t* tag = Carver::at<uint32_t>(sb, o_tag);
-    uint32_t* krow = has_mac ? Carver::at<uint32_t>(sb, o_krow) : nullptr;
-    uint32_t* perm = has_mac ? Carver::at<uint32_t>(sb, o_perm) : nullptr;
-    uint32_t* counts = Carver::at<uint32_t>(sb, o_counts);
-    uint32_t* nmac = counts + bkd::scrub::kBins;
-    bkd::ScrubClass cls[2];
-    int32_t* cst[2];
-    for (int c = 0; c < 2; ++c) {
-        cls[c] = bkd::ScrubClass{has[c] ? Carver::at<uint64_t>(sb, o_off[c]) : nullptr,
-                                 has[c] ? Carver::at<uint32_t>(sb, o_len[c]) : nullptr};
-        cst[c] = has[c] ? Carver::at<int32_t>(sb, o_st[c]) : nullptr;
-    }
-    const int order = g_scrub_order.load(std::memory_order_relaxed);
+    cv.bind(sb);
+    rc = scrub_order_lanes(st, d_log, log_size, d_offsets, d_lengths, n, a, cv, err, d_status, d_first_bad);
+    if (rc) return rc;
     const unsigned blocks = (unsigned)((n + bkd::kScrubBlock - 1) / bkd::kScrubBlock);
-    BKD_HIP(hipMemsetAsync(counts, 0, (bkd::scrub::kBins + 1) * 4, st));
-    const bkd::ScrubTable tab{a.ids, a.types, a.keys, a.nledgers, a.nkeys, a.mask};
-    hipLaunchKernelGGL(bkd::scrub_classify_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, (const uint8_t*)d_log,
-                       log_size, d_offsets, d_lengths, n, tab, cls[0], cls[1], tag, krow, counts, d_status, err);
-    BKD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(bkd::scrub_scan_kernel, dim3(1), dim3(1), 0, st, counts, nmac, n, order, d_first_bad);
-    BKD_HIP(hipGetLastError());
-    if (has_mac) {
-        hipLaunchKernelGGL(bkd::scrub_scatter_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, tag, n, order, counts,
-                           perm);
-        BKD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(bkd::mac_scrub_kernel, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, perm, nmac, tag, krow,
-                           a.key_states, a.nkeys, (const uint8_t*)d_log, d_offsets, d_lengths, n, d_status);
+    if (cv.has_mac) {
+        hipLaunchKernelGGL(bkd::mac_scrub_kernel, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, cv.perm, cv.nmac,
+                           cv.tag, cv.krow, a.key_states, a.nkeys, (const uint8_t*)d_log, d_offsets, d_lengths, n,
+                           d_status);
         BKD_HIP(hipGetLastError());
     }
     for (int c = 0; c < 2; ++c) {
-        if (!has[c]) continue;
-        const int vr = verify_framed(ds, st, c, 0, 0, 2, d_log, log_size, cls[c].off, cls[c].len, n, cst[c],
-                                     Carver::at<uint64_t>(sb, o_fb[c]));
+        if (!cv.has[c]) continue;
+        const int vr = verify_framed(ds, st, c, 0, 0, 2, d_log, log_size, cv.cls[c].off, cv.cls[c].len, n, cv.cst[c],
+                                     Carver::at<uint64_t>(sb, cv.o_fb[c]));
         if (vr) return vr;
     }
-    hipLaunchKernelGGL(bkd::scrub_merge_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, tag, cst[0], cst[1], n,
-                       d_status, (unsigned long long*)d_first_bad);
+    hipLaunchKernelGGL(bkd::scrub_merge_kernel, dim3(blocks), dim3(bkd::kScrubBlock), 0, st, cv.tag, cv.cst[0], cv.cst[1],
+                       n, d_status, (unsigned long long*)d_first_bad);
     BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
+// bkd_entrylog_scrub_lanes: the three launches above, then the lane array and the lane count copied out.
+int scrub_lanes(DeviceState& ds, hipStream_t st, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                const uint32_t* d_lengths, uint64_t n, const ScrubArgs& a, uint32_t* d_lanes, uint32_t* d_nlanes) {
+    if (n == 0) {
+        BKD_HIP(hipMemsetAsync(d_nlanes, 0, sizeof(uint32_t), st));
+        return BKD_OK;
+    }
+    uint32_t* err = nullptr;
+    int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    ScrubCarve cv(n, a.mask, true);
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);
+    uint8_t* sb = nullptr;
+    const hipError_t e = sc.get(4, cv.used, st, &sb);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("scrub scratch: ") + hipGetErrorString(e));
+    cv.bind(sb);
+    rc = scrub_order_lanes(st, d_log, log_size, d_offsets, d_lengths, n, a, cv, err, Carver::at<int32_t>(sb, cv.o_status),
+                           Carver::at<uint64_t>(sb, cv.o_first));
+    if (rc) return rc;
+    BKD_HIP(hipMemcpyAsync(d_lanes, cv.perm, n * 4, hipMemcpyDeviceToDevice, st));
+    BKD_HIP(hipMemcpyAsync(d_nlanes, cv.nmac, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     return BKD_OK;
 }
 
@@ -3281,6 +3343,22 @@ int bkd_get_scrub_host_route(const uint32_t* h_ledger_types, uint64_t nledgers, 
     if ((types >> bkd::scrub::kHmac) & 1u)
         for (uint64_t k = 0; h_ledger_types && k < nledgers && !mac; ++k) mac = h_ledger_types[k] == bkd::scrub::kHmac;
     return (mac && visible_devices() > 0) ? 2 : 1;
+}
+
+int bkd_entrylog_scrub_lanes(const void* d_log, uint64_t log_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                             uint64_t n, const int64_t* d_ledger_ids, const uint32_t* d_ledger_types,
+                             const uint32_t* d_ledger_keys, uint64_t nledgers, const uint32_t* d_key_states,
+                             uint64_t nkeys, uint32_t types, uint32_t* d_lanes, uint32_t* d_nlanes, void* stream) {
+    if (!d_nlanes) return fail(BKD_ERR_INVALID_ARG, "null nlanes");
+    if (n > 0 && !d_lanes) return fail(BKD_ERR_INVALID_ARG, "null lanes");
+    const ScrubArgs a{d_ledger_ids, d_ledger_types, d_ledger_keys, nledgers, d_key_states, nkeys, types};
+    const int rc = scrub_args_check(d_log, d_offsets, d_lengths, n, a, d_lanes, d_nlanes);
+    if (rc) return rc;
+    if (!((types >> bkd::scrub::kHmac) & 1u))
+        return fail(BKD_ERR_INVALID_ARG, "the lanes are the HMAC frames': types needs the HMAC bit");
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return scrub_lanes(*call.ds, call.st, d_log, log_size, d_offsets, d_lengths, n, a, d_lanes, d_nlanes);
 }
 
 uint32_t bkd_host_scrub_bin(uint32_t frame_len) { return bkd::scrub::bin(frame_len); }

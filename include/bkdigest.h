@@ -527,6 +527,20 @@ BKD_API int bkd_get_scrub_host_route(const uint32_t* h_ledger_types, uint64_t nl
  * two rules the device applies (scrub_rules.hpp). */
 BKD_API uint32_t bkd_host_scrub_bin(uint32_t frame_len);
 BKD_API int64_t bkd_host_scrub_lookup(const int64_t* ids, uint64_t nledgers, int64_t id);
+/* A hook for tests and tools: which entries the HMAC lanes of bkd_entrylog_verify_ledgers would take, and in
+ * which order. The arguments of that call without d_status and d_first_bad; `types` must hold the HMAC bit
+ * (BKD_ERR_INVALID_ARG otherwise, and for what that call refuses). Runs that call's classify, scan and
+ * scatter launches on `stream` (its status array comes from the stream's scratch), honours
+ * bkd_set_scrub_order and raises the stream's bounds flag as that call does; nothing is hashed. Then, on the
+ * stream: *d_nlanes = the lanes mac_scrub_kernel would run (order 0: the HMAC frames that are hashed; order
+ * 1: n) and d_lanes[0, n) = the permutation array, of which [0, *d_nlanes) is meaningful: lane s takes entry
+ * d_lanes[s] (order 0: bins descending, arbitrary inside a bin; order 1: the identity, lanes of other classes
+ * return at once). n == 0 writes *d_nlanes = 0. */
+BKD_API int bkd_entrylog_scrub_lanes(const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                                     const uint32_t* d_lengths, uint64_t n, const int64_t* d_ledger_ids,
+                                     const uint32_t* d_ledger_types, const uint32_t* d_ledger_keys,
+                                     uint64_t nledgers, const uint32_t* d_key_states, uint64_t nkeys,
+                                     uint32_t types, uint32_t* d_lanes, uint32_t* d_nlanes, void* stream);
 
 /* ---- MAC ledgers: batched HMAC-SHA1 (DigestType.MAC, MacDigestManager) ------------------
  * MacDigestManager ($BK/proto/checksum/MacDigestManager.java:46-107) digests with HmacSHA1 keyed with

@@ -61,42 +61,11 @@ def test_mixed_log(gpu, mixed, both_orders):
 
 # ---- 2. bins and wave cuts ----
 
-def shortest(b):
-    return max(52, 64 * (b - 1) + 12)
-
-
-def longest(b):
-    return 64 * b + 11
-
-
 def test_bins_and_wave_cuts(gpu, both_orders):
     """Frames at both ends of B = 1 .. 65 compressions; bins of 1, 63, 64 and 65 entries interleaved in arrival
-    order (a bin that ends inside a wave, on its edge, one past it); a corrupt frame in every bin."""
-    rng = np.random.default_rng(31)
-    ledgers = {100 + k: ("HMAC", b"pw%d" % (k % 3)) for k in range(5)}
-    table = el.LedgerTable.from_ledgers(ledgers)
-    by_bin = {}
-    for b in (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65):
-        for n in (shortest(b), longest(b)):
-            assert su.sha1_blocks(n) == b
-            by_bin.setdefault(su.bin_of(n), []).append(n)
-    assert su.sha1_blocks(shortest(2) - 1) == 1 and su.sha1_blocks(longest(2) + 1) == 3
-    entries, bins = [], []
-    for k, (bn, lengths) in enumerate(sorted(by_bin.items())):
-        count = (1, 63, 64, 65)[k % 4]
-        bad = int(rng.integers(count))
-        for j in range(count):
-            n = lengths[j % len(lengths)]
-            lid = 100 + int(rng.integers(5))
-            e = bytearray(su.frame_for(ledgers[lid], lid, j, rng.integers(0, 256, n - 52, dtype=np.uint8).tobytes()))
-            if j == bad:
-                e[int(rng.integers(8, n))] ^= 0x10
-            entries.append(bytes(e))
-            bins.append(bn)
-    order = rng.permutation(len(entries))
-    entries = [entries[i] for i in order]
-    buf, offs, lens = su.pack_entries(entries)
-    want = np.array([su.want_status(e, ledgers[int.from_bytes(e[:8], "big")]) for e in entries], dtype=np.int32)
+    order (a bin that ends inside a wave, on its edge, one past it); a corrupt frame in every bin (su.bins_log)."""
+    buf, offs, lens, table, want = su.bins_log()
+    by_bin = {su.bin_of(int(n)) for n in lens}
     assert (want == 2).sum() == len(by_bin) and len(by_bin) >= 12
     results = both_orders(lambda o: su.run_device(gpu, buf, offs, lens, table))
     for sync, status, fb in results:

@@ -159,6 +159,7 @@ with ck.host_batch_route(ck.HOST_ROUTE_GPU):
     assert rc == su.BKD_ERR_NO_DEVICE and (status == 77).all()
 p = 1 << 20  # the device-resident call is GPU work only
 assert _native.lib().bkd_entrylog_verify_ledgers(p, 64, p, p, 1, p, p, p, 1, p, 1, 15, p, p, None) == su.BKD_ERR_NO_DEVICE
+assert _native.lib().bkd_entrylog_scrub_lanes(p, 64, p, p, 1, p, p, p, 1, p, 1, 15, p, p, None) == su.BKD_ERR_NO_DEVICE
 print("scrub without a device")
 """
 
@@ -188,6 +189,22 @@ def test_device_call_argument_checks():
     assert call(p, 64, p, p, 1, p, p, p, 1, None, 1, 15, p, p, None) == inv     # HMAC bit, null key table
     assert call(p, 64, p, p, 1, p, p, p, 1, p, 0, 15, p, p, None) == inv        # HMAC bit, nkeys == 0
     assert call(p, 64, p, p, 1 << 32, p, p, p, 1, p, 1, 15, p, p, None) == inv  # n >= 2^32
+    lanes = L.bkd_entrylog_scrub_lanes  # the same checks, d_lanes / d_nlanes for d_status / d_first_bad
+    assert lanes(None, 64, p, p, 1, p, p, p, 1, p, 1, 15, p, p, None) == inv     # null log, n > 0
+    assert lanes(p, 64, None, p, 1, p, p, p, 1, p, 1, 15, p, p, None) == inv     # null offsets
+    assert lanes(p, 64, p, None, 1, p, p, p, 1, p, 1, 15, p, p, None) == inv     # null lengths
+    assert lanes(p, 64, p, p, 1, p, p, p, 1, p, 1, 15, None, p, None) == inv     # null lanes, n > 0
+    assert lanes(p, 64, p, p, 1, p, p, p, 1, p, 1, 15, p, None, None) == inv     # null nlanes
+    assert lanes(p, 64, p, p, 0, p, p, p, 1, p, 1, 15, None, None, None) == inv  # null nlanes, n == 0
+    assert lanes(p, 64, p, p, 1, None, p, p, 1, p, 1, 15, p, p, None) == inv     # null ledger ids, nledgers > 0
+    assert lanes(p, 64, p, p, 1, p, p, p, 1, p, 1, 16 | 4, p, p, None) == inv    # a type bit above 3
+    assert lanes(p, 64, p, p, 1, p, p, None, 1, p, 1, 15, p, p, None) == inv     # null key rows
+    assert lanes(p, 64, p, p, 1, p, p, p, 1, None, 1, 15, p, p, None) == inv     # null key table
+    assert lanes(p, 64, p, p, 1, p, p, p, 1, p, 0, 15, p, p, None) == inv        # nkeys == 0
+    assert lanes(p, 64, p, p, 1 << 32, p, p, p, 1, p, 1, 15, p, p, None) == inv  # n >= 2^32
+    for mask in (0, 1, 2, 8, 11):                                                # without the HMAC bit: no lanes
+        assert lanes(p, 64, p, p, 1, p, p, p, 1, p, 1, mask, p, p, None) == inv, mask
+        assert lanes(p, 64, p, p, 0, p, p, p, 1, p, 1, mask, p, p, None) == inv, mask
     assert L.bkd_set_scrub_order(2) == inv and L.bkd_set_scrub_order(-1) == inv
     assert L.bkd_set_scrub_order(1) == 0 and L.bkd_get_scrub_order() == 1
     assert L.bkd_set_scrub_order(0) == 0 and L.bkd_get_scrub_order() == 0
