@@ -137,6 +137,11 @@ PROTOTYPES = {
     "bkd_host_scrub_lookup": (_i64, [_vp, _u64, _i64]),
     "bkd_entrylog_scrub_lanes": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp,
                                         _vp]),
+    "bkd_entrylog_scrub_report": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp,
+                                         _vp, _u64, _vp, _vp]),
+    "bkd_entrylog_scrub_report_host": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp,
+                                              _vp, _vp, _u64, _vp]),
+    "bkd_entrylog_ledgers_map": (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "bkd_fill_splitmix64": (_int, [_vp, _u64, _u64, _u64, _vp]),
     "bkd_host_tables": (_i64, [_int, _int, _vp, _u64]),
     "bkd_host_gf_mul": (_u32, [_int, _u32, _u32]),

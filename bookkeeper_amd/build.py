@@ -21,7 +21,7 @@ HOST_SOURCES = [os.path.join(CSRC, "host_crc.cpp"), os.path.join(CSRC, "host_bat
 DEPS = SOURCES + HOST_SOURCES + [os.path.join(CSRC, f) for f in (
     "crc_kernels.hpp", "crc_tables.hpp", "plan_kernels.hpp", "host_crc.hpp", "host_batch.hpp",
     "host_mac.hpp", "mac_kernels.hpp", "mac_segments.hpp", "mac_sha1.hpp", "host_scrub.hpp", "scrub_kernels.hpp",
-    "scrub_rules.hpp")] + [os.path.join(ROOT, "include", "bkdigest.h")]
+    "scrub_rules.hpp", "scrub_report_kernels.hpp", "scrub_report_rules.hpp")] + [os.path.join(ROOT, "include", "bkdigest.h")]
 ARCH = os.environ.get("BKD_OFFLOAD_ARCH", "gfx950")
 
 

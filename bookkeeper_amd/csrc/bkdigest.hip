@@ -34,6 +34,7 @@
 #include "host_scrub.hpp"
 #include "mac_kernels.hpp"
 #include "scrub_kernels.hpp"
+#include "scrub_report_kernels.hpp"
 
 namespace {
 
@@ -2133,6 +2134,187 @@ int scrub_lanes(DeviceState& ds, hipStream_t st, const void* d_log, uint64_t log
     return BKD_OK;
 }
 
+// bkd_entrylog_scrub_report: scrub_ledgers as it is, then row init -> one lane per entry -> the scan of the
+// blocks' bad counts -> the bad list, over slot 4 carved as ScrubCarve with outputs of its own (the statuses
+// when the caller keeps none, the first_bad word) and the block counts behind it. The lock is taken here
+// and again by scrub_ledgers (it is recursive), whose smaller carve of slot 4 is a prefix of this one.
+int scrub_report(DeviceState& ds, hipStream_t st, const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                 const uint32_t* d_lengths, uint64_t n, const ScrubArgs& a, int32_t* d_status, uint64_t* d_report,
+                 uint32_t* d_bad, uint64_t bad_capacity, uint64_t* d_nbad) {
+    const uint64_t rows = a.nledgers + 1;
+    const unsigned init_blocks = (unsigned)((rows * bkd::scrub::kReportWords + bkd::kReportBlock - 1) / bkd::kReportBlock);
+    hipLaunchKernelGGL(bkd::scrub_report_init_kernel, dim3(init_blocks), dim3(bkd::kReportBlock), 0, st, d_report, rows, n);
+    BKD_HIP(hipGetLastError());
+    if (n == 0) {
+        BKD_HIP(hipMemsetAsync(d_nbad, 0, sizeof(uint64_t), st));
+        return BKD_OK;
+    }
+    const uint64_t blocks = (n + bkd::kReportBlock - 1) / bkd::kReportBlock;
+    ScrubCarve cv(n, a.mask, true);
+    Carver more;
+    more.used = cv.used;
+    const size_t o_blocks = more.take(blocks * 4);
+    StreamScratch& sc = scratch_for(ds, st);
+    std::lock_guard<std::recursive_mutex> lk(sc.mu);
+    uint8_t* sb = nullptr;
+    const hipError_t e = sc.get(4, more.used, st, &sb);
+    if (e != hipSuccess) return fail(BKD_ERR_NOMEM, std::string("scrub scratch: ") + hipGetErrorString(e));
+    int32_t* status = d_status ? d_status : Carver::at<int32_t>(sb, cv.o_status);
+    const int rc = scrub_ledgers(ds, st, d_log, log_size, d_offsets, d_lengths, n, a, status,
+                                 Carver::at<uint64_t>(sb, cv.o_first));
+    if (rc) return rc;
+    uint32_t* block_bad = Carver::at<uint32_t>(sb, o_blocks);
+    hipLaunchKernelGGL(bkd::scrub_report_kernel, dim3((unsigned)blocks), dim3(bkd::kReportBlock), 0, st,
+                       (const uint8_t*)d_log, log_size, d_offsets, d_lengths, n, a.ids, a.nledgers, status,
+                       (unsigned long long*)d_report, block_bad);
+    BKD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bkd::scrub_report_scan_kernel, dim3(1), dim3(bkd::kReportScanBlock), 0, st, block_bad, blocks,
+                       d_nbad);
+    BKD_HIP(hipGetLastError());
+    if (bad_capacity) {
+        hipLaunchKernelGGL(bkd::scrub_report_scatter_kernel, dim3((unsigned)blocks), dim3(bkd::kReportBlock), 0, st, status,
+                           n, block_bad, d_bad, bad_capacity);
+        BKD_HIP(hipGetLastError());
+    }
+    return BKD_OK;
+}
+
+// The extra argument checks of the report calls, after scrub_args_check.
+int report_args_check(const void* report, const void* bad, uint64_t bad_capacity, const void* nbad) {
+    if (!report) return fail(BKD_ERR_INVALID_ARG, "null report");
+    if (!nbad) return fail(BKD_ERR_INVALID_ARG, "null nbad");
+    if (bad_capacity > 0 && !bad) return fail(BKD_ERR_INVALID_ARG, "null bad list with a capacity above 0");
+    return BKD_OK;
+}
+
+// The host forms' upload into plain allocations on a stream of the call's own, so that its bounds flag is
+// its own; everything is freed when the call returns.
+struct HostUpload {
+    std::vector<void*> ptrs;
+    hipStream_t st = nullptr;
+    bool failed = false;
+    ~HostUpload() {
+        for (void* p : ptrs) (void)hipFree(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    void* get(size_t bytes) {  // nullptr on failure (or for no bytes)
+        if (!bytes) return nullptr;
+        void* d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            failed = true;
+            return nullptr;
+        }
+        ptrs.push_back(d);
+        return d;
+    }
+    void* put(const void* h, size_t bytes) {  // nullptr on failure (or for nothing to copy)
+        if (!h) return nullptr;
+        void* d = get(bytes);
+        if (d && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) failed = true;
+        return d;
+    }
+};
+
+// The report outputs of bkd_entrylog_scrub_report_host in host memory.
+struct HostReport {
+    uint64_t* report;
+    uint32_t* bad;
+    uint64_t capacity;
+    uint64_t* nbad;
+};
+
+// bkd_entrylog_verify_ledgers_host (rep null) and bkd_entrylog_scrub_report_host (h_status and h_first_bad
+// may be null) after their argument checks: the table check, the route, and everything written before
+// BKD_ERR_BOUNDS is returned.
+int scrub_host(const void* h_log, uint64_t log_size, const uint64_t* h_offsets, const uint32_t* h_lengths, uint64_t n,
+               const ScrubArgs& a, int32_t* h_status, uint64_t* h_first_bad, const HostReport* rep) {
+    const bkd::host::ScrubLedgers t{a.ids, a.types, a.keys, a.nledgers, a.key_states, a.nkeys, a.mask};
+    if (const uint64_t bad = bkd::host::scrub_table_check(t))
+        return fail(BKD_ERR_INVALID_ARG, "ledger table row " + std::to_string(bad - 1) +
+                                             ": ids must ascend strictly and an HMAC row's key index be < nkeys");
+    uint64_t first_bad_word = 0;
+    if (!h_first_bad) h_first_bad = &first_bad_word;
+    if (n == 0) {
+        *h_first_bad = 0;
+        if (rep)  // the initial rows, *nbad = 0
+            bkd::host::scrub_report(nullptr, log_size, nullptr, nullptr, 0, t, nullptr, rep->report, rep->bad,
+                                    rep->capacity, rep->nbad);
+        return BKD_OK;
+    }
+    const int route = bkd_get_scrub_host_route(a.types, a.nledgers, a.mask);
+    if (route == 1) {
+        std::vector<int32_t> own;
+        if (!h_status) {
+            own.resize(n);
+            h_status = own.data();
+        }
+        const bool unreadable =
+            bkd::host::scrub_entries((const uint8_t*)h_log, log_size, h_offsets, h_lengths, n, t, h_status, h_first_bad);
+        if (rep)
+            bkd::host::scrub_report((const uint8_t*)h_log, log_size, h_offsets, h_lengths, n, t, h_status, rep->report,
+                                    rep->bad, rep->capacity, rep->nbad);
+        return unreadable ? fail(BKD_ERR_BOUNDS, kBoundsMsg) : BKD_OK;
+    }
+    if (visible_devices() <= 0) return fail(BKD_ERR_NO_DEVICE, "no HIP device (host batch route forced to the GPU)");
+    // one upload into plain allocations on a stream of the call's own, so that its bounds flag is its own
+    HostUpload dev;
+    BKD_HIP(hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking));
+    // the log rounded up to whole dwords: the last entry's last aligned dword lies inside the allocation
+    const size_t log_alloc = ((size_t)log_size + 3u) & ~(size_t)3u;
+    void* d_log = nullptr;
+    if (log_alloc) {
+        if (hipMalloc(&d_log, log_alloc) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BKD_ERR_NOMEM, "scrub: device allocation for the log failed");
+        }
+        dev.ptrs.push_back(d_log);
+        BKD_HIP(hipMemcpy(d_log, h_log, log_size, hipMemcpyHostToDevice));
+    }
+    const uint64_t* d_off = (const uint64_t*)dev.put(h_offsets, n * 8);
+    const uint32_t* d_len = (const uint32_t*)dev.put(h_lengths, n * 4);
+    const ScrubArgs da{(const int64_t*)dev.put(a.ids, a.nledgers * 8),
+                       (const uint32_t*)dev.put(a.types, a.nledgers * 4),
+                       (const uint32_t*)dev.put(a.keys, a.nledgers * 4),
+                       a.nledgers,
+                       (const uint32_t*)dev.put(a.key_states, a.nkeys * 40),
+                       a.nkeys,
+                       a.mask};
+    int32_t* d_status = nullptr;
+    if (h_status) {
+        std::vector<int32_t> none(n, 0);
+        d_status = (int32_t*)dev.put(none.data(), n * 4);
+    }
+    uint64_t* d_fb = rep ? nullptr : (uint64_t*)dev.put(&n, 8);
+    const uint64_t rows = a.nledgers + 1, list = rep ? std::min(rep->capacity, n) : 0;
+    uint64_t* d_report = rep ? (uint64_t*)dev.get(rows * bkd::scrub::kReportWords * 8) : nullptr;
+    uint32_t* d_bad = rep ? (uint32_t*)dev.get(list * 4) : nullptr;
+    uint64_t* d_nbad = rep ? (uint64_t*)dev.get(8) : nullptr;
+    if (dev.failed) return fail(BKD_ERR_NOMEM, "scrub: device allocation or upload failed");
+    int rc;
+    {
+        Call call((void*)dev.st);
+        if (call.rc) return call.rc;
+        rc = rep ? scrub_report(*call.ds, call.st, d_log, log_size, d_off, d_len, n, da, d_status, d_report, d_bad, list,
+                                d_nbad)
+                 : scrub_ledgers(*call.ds, call.st, d_log, log_size, d_off, d_len, n, da, d_status, d_fb);
+    }
+    // waits for the stream, frees its scratch and reports its bounds flag, whatever the launches answered
+    const int rel = bkd_stream_release((void*)dev.st);
+    if (rc) return rc;
+    if (rel && rel != BKD_ERR_BOUNDS) return rel;
+    if (h_status) BKD_HIP(hipMemcpy(h_status, d_status, n * 4, hipMemcpyDeviceToHost));
+    if (!rep) {
+        BKD_HIP(hipMemcpy(h_first_bad, d_fb, 8, hipMemcpyDeviceToHost));
+        return rel;
+    }
+    BKD_HIP(hipMemcpy(rep->report, d_report, rows * bkd::scrub::kReportWords * 8, hipMemcpyDeviceToHost));
+    BKD_HIP(hipMemcpy(rep->nbad, d_nbad, 8, hipMemcpyDeviceToHost));
+    const uint64_t listed = std::min(*rep->nbad, list);
+    if (listed) BKD_HIP(hipMemcpy(rep->bad, d_bad, listed * 4, hipMemcpyDeviceToHost));
+    return rel;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3249,82 +3431,56 @@ int bkd_entrylog_verify_ledgers_host(const void* h_log, uint64_t log_size, const
                                      const uint32_t* h_key_states, uint64_t nkeys, uint32_t types, int32_t* h_status,
                                      uint64_t* h_first_bad) {
     const ScrubArgs a{h_ledger_ids, h_ledger_types, h_ledger_keys, nledgers, h_key_states, nkeys, types};
-    int rc = scrub_args_check(h_log, h_offsets, h_lengths, n, a, h_status, h_first_bad);
+    const int rc = scrub_args_check(h_log, h_offsets, h_lengths, n, a, h_status, h_first_bad);
     if (rc) return rc;
-    const bkd::host::ScrubLedgers t{h_ledger_ids, h_ledger_types, h_ledger_keys, nledgers, h_key_states, nkeys, types};
-    if (const uint64_t bad = bkd::host::scrub_table_check(t))
-        return fail(BKD_ERR_INVALID_ARG, "ledger table row " + std::to_string(bad - 1) +
-                                             ": ids must ascend strictly and an HMAC row's key index be < nkeys");
-    if (n == 0) {
-        *h_first_bad = 0;
-        return BKD_OK;
-    }
-    const int route = bkd_get_scrub_host_route(h_ledger_types, nledgers, types);
-    if (route == 1) {
-        const bool unreadable =
-            bkd::host::scrub_entries((const uint8_t*)h_log, log_size, h_offsets, h_lengths, n, t, h_status, h_first_bad);
-        return unreadable ? fail(BKD_ERR_BOUNDS, kBoundsMsg) : BKD_OK;
-    }
-    if (visible_devices() <= 0) return fail(BKD_ERR_NO_DEVICE, "no HIP device (host batch route forced to the GPU)");
-    // one upload into plain allocations on a stream of the call's own, so that its bounds flag is its own
-    struct Dev {
-        std::vector<void*> ptrs;
-        hipStream_t st = nullptr;
-        ~Dev() {
-            for (void* p : ptrs) (void)hipFree(p);
-            if (st) (void)hipStreamDestroy(st);
-        }
-        void* put(const void* h, size_t bytes) {  // nullptr on failure (or for nothing to copy)
-            if (!h || !bytes) return nullptr;
-            void* d = nullptr;
-            if (hipMalloc(&d, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                failed = true;
-                return nullptr;
-            }
-            ptrs.push_back(d);
-            if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) failed = true;
-            return d;
-        }
-        bool failed = false;
-    } dev;
-    BKD_HIP(hipStreamCreateWithFlags(&dev.st, hipStreamNonBlocking));
-    // the log rounded up to whole dwords: the last entry's last aligned dword lies inside the allocation
-    const size_t log_alloc = ((size_t)log_size + 3u) & ~(size_t)3u;
-    void* d_log = nullptr;
-    if (log_alloc) {
-        if (hipMalloc(&d_log, log_alloc) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BKD_ERR_NOMEM, "scrub: device allocation for the log failed");
-        }
-        dev.ptrs.push_back(d_log);
-        BKD_HIP(hipMemcpy(d_log, h_log, log_size, hipMemcpyHostToDevice));
-    }
-    const uint64_t* d_off = (const uint64_t*)dev.put(h_offsets, n * 8);
-    const uint32_t* d_len = (const uint32_t*)dev.put(h_lengths, n * 4);
-    const ScrubArgs da{(const int64_t*)dev.put(h_ledger_ids, nledgers * 8),
-                       (const uint32_t*)dev.put(h_ledger_types, nledgers * 4),
-                       (const uint32_t*)dev.put(h_ledger_keys, nledgers * 4),
-                       nledgers,
-                       (const uint32_t*)dev.put(h_key_states, nkeys * 40),
-                       nkeys,
-                       types};
-    std::vector<int32_t> none(n, 0);
-    int32_t* d_status = (int32_t*)dev.put(none.data(), n * 4);
-    uint64_t* d_fb = (uint64_t*)dev.put(&n, 8);
-    if (dev.failed) return fail(BKD_ERR_NOMEM, "scrub: device allocation or upload failed");
-    {
-        Call call((void*)dev.st);
-        if (call.rc) return call.rc;
-        rc = scrub_ledgers(*call.ds, call.st, d_log, log_size, d_off, d_len, n, da, d_status, d_fb);
-    }
-    // waits for the stream, frees its scratch and reports its bounds flag, whatever the launches answered
-    const int rel = bkd_stream_release((void*)dev.st);
+    return scrub_host(h_log, log_size, h_offsets, h_lengths, n, a, h_status, h_first_bad, nullptr);
+}
+
+int bkd_entrylog_scrub_report(const void* d_log, uint64_t log_size, const uint64_t* d_offsets, const uint32_t* d_lengths,
+                              uint64_t n, const int64_t* d_ledger_ids, const uint32_t* d_ledger_types,
+                              const uint32_t* d_ledger_keys, uint64_t nledgers, const uint32_t* d_key_states,
+                              uint64_t nkeys, uint32_t types, int32_t* d_status, uint64_t* d_report, uint32_t* d_bad,
+                              uint64_t bad_capacity, uint64_t* d_nbad, void* stream) {
+    const ScrubArgs a{d_ledger_ids, d_ledger_types, d_ledger_keys, nledgers, d_key_states, nkeys, types};
+    int rc = report_args_check(d_report, d_bad, bad_capacity, d_nbad);
     if (rc) return rc;
-    if (rel && rel != BKD_ERR_BOUNDS) return rel;
-    BKD_HIP(hipMemcpy(h_status, d_status, n * 4, hipMemcpyDeviceToHost));
-    BKD_HIP(hipMemcpy(h_first_bad, d_fb, 8, hipMemcpyDeviceToHost));
-    return rel;
+    rc = scrub_args_check(d_log, d_offsets, d_lengths, n, a, d_report, d_nbad);  // d_status may be null
+    if (rc) return rc;
+    Call call(stream);
+    if (call.rc) return call.rc;
+    return scrub_report(*call.ds, call.st, d_log, log_size, d_offsets, d_lengths, n, a, d_status, d_report, d_bad,
+                        bad_capacity, d_nbad);
+}
+
+int bkd_entrylog_scrub_report_host(const void* h_log, uint64_t log_size, const uint64_t* h_offsets,
+                                   const uint32_t* h_lengths, uint64_t n, const int64_t* h_ledger_ids,
+                                   const uint32_t* h_ledger_types, const uint32_t* h_ledger_keys, uint64_t nledgers,
+                                   const uint32_t* h_key_states, uint64_t nkeys, uint32_t types, int32_t* h_status,
+                                   uint64_t* h_report, uint32_t* h_bad, uint64_t bad_capacity, uint64_t* h_nbad) {
+    const ScrubArgs a{h_ledger_ids, h_ledger_types, h_ledger_keys, nledgers, h_key_states, nkeys, types};
+    int rc = report_args_check(h_report, h_bad, bad_capacity, h_nbad);
+    if (rc) return rc;
+    rc = scrub_args_check(h_log, h_offsets, h_lengths, n, a, h_report, h_nbad);  // h_status may be null
+    if (rc) return rc;
+    const HostReport rep{h_report, h_bad, bad_capacity, h_nbad};
+    return scrub_host(h_log, log_size, h_offsets, h_lengths, n, a, h_status, nullptr, &rep);
+}
+
+int bkd_entrylog_ledgers_map(const void* h_log, uint64_t log_size, int64_t* h_ledger_ids, int64_t* h_sizes,
+                             uint64_t capacity, uint64_t* h_count, int32_t* h_version, int64_t* h_map_offset,
+                             int32_t* h_ledgers_count, int32_t* h_state) {
+    if (!h_count || !h_state || (log_size && !h_log) || (capacity && (!h_ledger_ids || !h_sizes)))
+        return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    const bkd::host::LedgersMap m =
+        bkd::host::read_ledgers_map((const uint8_t*)h_log, log_size, h_ledger_ids, h_sizes, capacity);
+    *h_count = m.count;
+    *h_state = m.state;
+    if (h_version) *h_version = m.version;
+    if (h_map_offset) *h_map_offset = m.map_offset;
+    if (h_ledgers_count) *h_ledgers_count = m.ledgers_count;
+    if (m.state == BKD_LEDGERS_MAP_MALFORMED) (void)fail(BKD_OK, std::string("ledgers map: ") + m.why);
+    if (m.over) return fail(BKD_ERR_BOUNDS, "ledgers map capacity exceeded");
+    return BKD_OK;
 }
 
 int bkd_set_scrub_order(int order) {

@@ -7,6 +7,7 @@
 #include "../../include/bkdigest.h"
 #include "host_batch.hpp"
 #include "host_mac.hpp"
+#include "scrub_report_rules.hpp"
 #include "scrub_rules.hpp"
 
 namespace bkd {
@@ -109,6 +110,107 @@ bool scrub_entries(const uint8_t* log, uint64_t log_size, const uint64_t* offset
         }
     *first_bad = fb;
     return unreadable;
+}
+
+void scrub_report(const uint8_t* log, uint64_t log_size, const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
+                  const ScrubLedgers& t, const int32_t* status, uint64_t* report, uint32_t* bad, uint64_t capacity,
+                  uint64_t* nbad) {
+    for (uint64_t r = 0; r <= t.nledgers; ++r)
+        for (uint32_t w = 0; w < scrub::kReportWords; ++w) report[r * scrub::kReportWords + w] = scrub::initial_word(w, n);
+    uint64_t found = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t o = offsets[i];
+        const uint32_t l = lengths[i];
+        const bool in_log = scrub::in_range(o, l, log_size);
+        int64_t looked_up = -1;
+        if (scrub::has_ledger_id(in_log, l)) {
+            uint64_t be = 0;
+            for (int k = 0; k < 8; ++k) be = (be << 8) | log[o + k];
+            looked_up = scrub::lookup(t.ids, t.nledgers, (int64_t)be);
+        }
+        uint64_t* r = report + scrub::report_row(looked_up, t.nledgers) * scrub::kReportWords;
+        const uint32_t word = scrub::status_word(status[i]);
+        r[BKD_REPORT_ENTRIES] += 1;
+        r[BKD_REPORT_BYTES] += scrub::report_bytes(l);
+        r[word] += 1;
+        if (word != BKD_REPORT_BAD) continue;
+        if (found < capacity) bad[found] = (uint32_t)i;
+        ++found;
+        if (i < r[BKD_REPORT_FIRST_BAD_INDEX]) r[BKD_REPORT_FIRST_BAD_INDEX] = i;
+        if (scrub::has_entry_id(in_log, l)) {
+            uint64_t be = 0;
+            for (int k = 8; k < 16; ++k) be = (be << 8) | log[o + k];
+            const int64_t eid = (int64_t)be;
+            if (eid < (int64_t)r[BKD_REPORT_MIN_BAD_ENTRY]) r[BKD_REPORT_MIN_BAD_ENTRY] = (uint64_t)eid;
+            if (eid > (int64_t)r[BKD_REPORT_MAX_BAD_ENTRY]) r[BKD_REPORT_MAX_BAD_ENTRY] = (uint64_t)eid;
+        }
+    }
+    *nbad = found;
+}
+
+LedgersMap read_ledgers_map(const uint8_t* log, uint64_t log_size, int64_t* ledger_ids, int64_t* sizes,
+                            uint64_t capacity) {
+    LedgersMap m;
+    auto be32 = [&](uint64_t at) {
+        return (int32_t)(((uint32_t)log[at] << 24) | ((uint32_t)log[at + 1] << 16) | ((uint32_t)log[at + 2] << 8) |
+                         (uint32_t)log[at + 3]);
+    };
+    auto be64 = [&](uint64_t at) {
+        uint64_t v = 0;
+        for (int k = 0; k < 8; ++k) v = (v << 8) | log[at + k];
+        return (int64_t)v;
+    };
+    auto malformed = [&](const char* why) {
+        m.state = BKD_LEDGERS_MAP_MALFORMED;
+        m.why = why;
+        return m;
+    };
+    if (log_size < 20) return malformed("short read of the log header");
+    m.version = be32(4);
+    m.map_offset = be64(8);
+    m.ledgers_count = be32(16);
+    if (m.version < 1 || m.map_offset == 0) {
+        m.state = BKD_LEDGERS_MAP_ABSENT;
+        return m;
+    }
+    if (m.map_offset < 0) return malformed("short read: a negative ledgers map offset");
+    std::vector<int64_t> seen;
+    uint64_t offset = (uint64_t)m.map_offset;
+    while (offset < log_size) {
+        if (log_size - offset < 4) return malformed("short read of a record's size");
+        const int32_t map_size = be32(offset);
+        if (map_size <= 0) break;
+        const uint64_t body = offset + 4, len = (uint64_t)map_size;
+        if (len > log_size - body) return malformed("short read: a record cut by the end of the buffer");
+        // inside the record, in the order the reference reads it
+        if (len < 8) return malformed("a record shorter than its fields");
+        if (be64(body) != -1) return malformed("a record's ledger id is not -1");
+        if (len < 16) return malformed("a record shorter than its fields");
+        if (be64(body + 8) != -2) return malformed("a record's entry id is not -2");
+        if (len < 20) return malformed("a record shorter than its fields");
+        const int32_t count = be32(body + 16);
+        uint64_t at = 20;
+        for (int32_t k = 0; k < count; ++k, at += 16) {
+            if (len - at < 16) return malformed("a record shorter than its count implies");
+            const int64_t lid = be64(body + at), sz = be64(body + at + 8);
+            if (m.count < capacity) {
+                ledger_ids[m.count] = lid;
+                sizes[m.count] = sz;
+            } else {
+                m.over = true;
+            }
+            ++m.count;
+            seen.push_back(lid);
+        }
+        if (at != len) return malformed("a record longer than its count implies");
+        offset = body + len;
+    }
+    std::sort(seen.begin(), seen.end());
+    const uint64_t distinct = (uint64_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+    if ((int64_t)distinct != (int64_t)m.ledgers_count)
+        return malformed("the distinct ledgers of the map are not as many as the header's count");
+    if (m.ledgers_count == 0) return malformed("a header count of 0");
+    return m;
 }
 
 }  // namespace host

@@ -28,5 +28,24 @@ uint64_t scrub_table_check(const ScrubLedgers& t);
 bool scrub_entries(const uint8_t* log, uint64_t log_size, const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
                    const ScrubLedgers& t, int32_t* status, uint64_t* first_bad);
 
+// The report of bkd_entrylog_scrub_report from the statuses above, one serial pass with the rules the device
+// applies (scrub_report_rules.hpp): report[(nledgers + 1) x 8], bad[0, min(*nbad, capacity)) ascending.
+void scrub_report(const uint8_t* log, uint64_t log_size, const uint64_t* offsets, const uint32_t* lengths, uint64_t n,
+                  const ScrubLedgers& t, const int32_t* status, uint64_t* report, uint32_t* bad, uint64_t capacity,
+                  uint64_t* nbad);
+
+// What bkd_entrylog_ledgers_map reads (include/bkdigest.h). `why` names the case of a malformed map.
+struct LedgersMap {
+    int32_t version = 0;
+    int64_t map_offset = 0;
+    int32_t ledgers_count = 0;
+    int32_t state = 0;     // BKD_LEDGERS_MAP_*
+    uint64_t count = 0;    // pairs written
+    bool over = false;     // more pairs than the capacity
+    const char* why = "";
+};
+LedgersMap read_ledgers_map(const uint8_t* log, uint64_t log_size, int64_t* ledger_ids, int64_t* sizes,
+                            uint64_t capacity);
+
 }  // namespace host
 }  // namespace bkd

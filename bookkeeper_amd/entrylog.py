@@ -12,7 +12,11 @@ them back with ``scanEntryLog`` (:995-1060). It never re-verifies their digests 
 * ``LedgerTable`` / ``EntryLogScrubber.verify_ledgers`` — a log that mixes CRC32C, CRC32, HMAC and DUMMY
   ledgers in one device call (``bkd_entrylog_verify_ledgers``): the ledger of every entry is looked up on
   the device and the HMAC frames are hashed in lanes binned by length; ``verify_ledgers_host`` from host
-  memory.
+  memory;
+* ``EntryLogScrubber.report_ledgers`` / ``ScrubReport`` — the same scrub with its per-ledger rows (entries,
+  bytes, ok / bad / not checked, the range of bad entry ids) and the ascending list of bad entries made on
+  the device (``bkd_entrylog_scrub_report``); ``read_ledgers_map`` reads the log's own ledgers map
+  (``bkd_entrylog_ledgers_map``) and ``ScrubReport.compare_ledgers_map`` holds the two against each other.
 """
 from __future__ import annotations
 
@@ -21,7 +25,7 @@ import ctypes
 import numpy as np
 
 from . import checksum as _ck
-from ._native import CRC32, CRC32C, check, lib
+from ._native import CRC32, CRC32C, check, last_error, lib
 
 BKD_ERR_BOUNDS = -4
 
@@ -132,6 +136,112 @@ def _ptr(a: np.ndarray):
     return ctypes.c_void_p(a.ctypes.data if a.size else 0)
 
 
+def _default_mask(table: LedgerTable, types) -> int:
+    mask = DIGEST_ALL if types is None else int(types)
+    if types is None and not table.nkeys:
+        mask &= ~(1 << DIGEST_HMAC)  # no HMAC ledger listed: the call needs no key table
+    return mask
+
+
+REPORT_WORDS = 8  # BKD_SCRUB_REPORT_WORDS
+DEFAULT_MAX_BAD = 4096
+# a row of the report as a structured record; the entry ids are signed (BKD_REPORT_*)
+REPORT_DTYPE = np.dtype([("entries", np.uint64), ("bytes", np.uint64), ("ok", np.uint64), ("bad", np.uint64),
+                         ("not_checked", np.uint64), ("min_bad_entry", np.int64), ("max_bad_entry", np.int64),
+                         ("first_bad_index", np.uint64)])
+LEDGERS_MAP_READ, LEDGERS_MAP_ABSENT, LEDGERS_MAP_MALFORMED = 0, 1, 2  # BKD_LEDGERS_MAP_*
+
+
+class LedgersMap:
+    """What ``read_ledgers_map`` found: the (ledger id, size) pairs as they lie in the log, the header's
+    version, ledgersMapOffset and ledgersCount, the state (LEDGERS_MAP_*) and, for a malformed map, why."""
+
+    def __init__(self, ledger_ids, sizes, version: int, map_offset: int, ledgers_count: int, state: int, why: str):
+        self.ledger_ids = ledger_ids
+        self.sizes = sizes
+        self.version = version
+        self.map_offset = map_offset
+        self.ledgers_count = ledgers_count
+        self.state = state
+        self.why = why
+
+    def totals(self) -> dict:
+        """{ledger id: size}, the sizes of duplicate rows added up as EntryLogMetadata.addLedgerSize does."""
+        out: dict[int, int] = {}
+        for lid, size in zip(self.ledger_ids.tolist(), self.sizes.tolist()):
+            out[lid] = out.get(lid, 0) + size
+        return out
+
+
+def read_ledgers_map(log) -> LedgersMap:
+    """The log's ledgers map (``bkd_entrylog_ledgers_map``), read as
+    DefaultEntryLogger.extractEntryLogMetadataFromIndex (:1089-1176) reads it. Host control logic."""
+    buf = _ck._host_view(log)
+    count = ctypes.c_uint64(0)
+    version, ledgers_count, state = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    map_offset = ctypes.c_int64(0)
+    cap = 64
+    while True:
+        lids = np.zeros(cap, dtype=np.int64)
+        sizes = np.zeros(cap, dtype=np.int64)
+        rc = lib().bkd_entrylog_ledgers_map(_ptr(buf), buf.size, _ptr(lids), _ptr(sizes), cap, ctypes.byref(count),
+                                            ctypes.byref(version), ctypes.byref(map_offset),
+                                            ctypes.byref(ledgers_count), ctypes.byref(state))
+        if rc == BKD_ERR_BOUNDS and int(count.value) > cap:
+            cap = int(count.value)
+            continue
+        check(rc)
+        break
+    why = last_error() if state.value == LEDGERS_MAP_MALFORMED else ""
+    k = int(count.value)
+    return LedgersMap(lids[:k].copy(), sizes[:k].copy(), int(version.value), int(map_offset.value),
+                      int(ledgers_count.value), int(state.value), why)
+
+
+class ScrubReport:
+    """A scrub as it is read (``bkd_entrylog_scrub_report``): `scan`; `rows`, one REPORT_DTYPE record per row
+    of `table` (rows[r] belongs to table.ids[r]); `other`, the catch-all row (unlisted ledgers, entries out of
+    range or under 8 bytes); `nbad`, all bad entries; `bad`, the lowest indices of them, ascending; `status`,
+    the n statuses when they were asked for."""
+
+    def __init__(self, scan: ScanResult, table: LedgerTable, words: np.ndarray, nbad: int, bad: np.ndarray,
+                 log_host=None, status=None):
+        recs = np.ascontiguousarray(words, dtype=np.uint64).view(REPORT_DTYPE)
+        self.scan = scan
+        self.table = table
+        self.rows = recs[:len(table)]
+        self.other = recs[len(table)]
+        self.nbad = int(nbad)
+        self.bad = np.asarray(bad, dtype=np.uint32)
+        self.status = status
+        self._log = log_host
+
+    def bad_entries(self) -> list:
+        """(ledger id, entry id, offset, length) of every listed bad entry, from the scan and the host log;
+        the entry id is None where the entry is shorter than 16 bytes."""
+        buf = _ck._host_view(self._log)
+        out = []
+        for i in self.bad.tolist():
+            o, n = int(self.scan.offsets[i]), int(self.scan.lengths[i])
+            eid = int.from_bytes(bytes(buf[o + 8:o + 16]), "big", signed=True) if n >= 16 and o + n <= buf.size else None
+            out.append((int(self.scan.ledger_ids[i]), eid, o, n))
+        return out
+
+    def damaged(self) -> dict:
+        """{ledger id: (bad entries, lowest bad entry id, highest)} for the table's rows with bad entries."""
+        return {int(self.table.ids[r]): (int(row["bad"]), int(row["min_bad_entry"]), int(row["max_bad_entry"]))
+                for r, row in enumerate(self.rows) if row["bad"] > 0}
+
+    def compare_ledgers_map(self, ledgers_map: LedgersMap):
+        """The scan against the log's own map: (ledgers whose scanned bytes differ from the map's size as
+        {ledger id: (scanned, map)}, ledgers in the map only, ledgers in the table only), the last two sorted.
+        A ledger of the table that the log holds no entry of counts as absent from the scan."""
+        totals = ledgers_map.totals()
+        scanned = {int(self.table.ids[r]): int(row["bytes"]) for r, row in enumerate(self.rows) if row["entries"] > 0}
+        differ = {l: (scanned[l], totals[l]) for l in scanned if l in totals and scanned[l] != totals[l]}
+        return differ, sorted(set(totals) - set(scanned)), sorted(set(scanned) - set(totals))
+
+
 class EntryLogScrubber:
     """Verifies the digests of all entries of one entry log on the GPU.
 
@@ -233,3 +343,71 @@ class EntryLogScrubber:
             _ptr(table.keys), len(table), _ptr(table.key_states), table.nkeys, mask, _ptr(status),
             ctypes.byref(first_bad)))
         return scan, status, int(first_bad.value)
+
+    @staticmethod
+    def report_ledgers(log_host, table: LedgerTable, log_device=None, types=None, stream=None,
+                       start: int = LOGFILE_HEADER_SIZE, max_bad: int = DEFAULT_MAX_BAD, want_status: bool = False):
+        """The scrub of ``verify_ledgers`` with what it is read for made on the device
+        (``bkd_entrylog_scrub_report``): one row per ledger and the ascending list of bad entries (the lowest
+        `max_bad` of them). Only the rows, the count and the list come back from the device; the n statuses
+        stay there unless `want_status`. Returns a ``ScrubReport``; raises BkdError(BKD_ERR_BOUNDS) as
+        ``verify_ledgers`` does."""
+        import torch
+        scan = scan_entry_log(log_host, start)
+        n = len(scan)
+        if log_device is None:
+            host = _ck._host_view(log_host)
+            padded = np.zeros(max(4, (host.size + 3) & ~3), dtype=np.uint8)  # whole dwords: the last entry's last load
+            padded[:host.size] = host
+            log_device = torch.from_numpy(padded).cuda()
+            log_size = host.size
+        else:
+            log_size = log_device.numel() * log_device.element_size()
+        dev = log_device.device
+        mask = _default_mask(table, types)
+        d_ids, d_types, d_keys, d_states = table.on(dev)
+        d_off = torch.from_numpy(scan.offsets.astype(np.int64)).to(dev)
+        d_len = torch.from_numpy(scan.lengths.astype(np.int32)).to(dev)
+        cap = min(int(max_bad), n)
+        d_status = torch.empty(n, dtype=torch.int32, device=dev) if want_status and n else None
+        d_report = torch.empty((len(table) + 1) * REPORT_WORDS, dtype=torch.int64, device=dev)
+        d_bad = torch.empty(cap, dtype=torch.int32, device=dev) if cap else None
+        d_nbad = torch.empty(1, dtype=torch.int64, device=dev)
+
+        def ptr(t, what, dtype=None):
+            return _ck._dev_ptr(t, what, dtype) if t is not None and t.numel() else None
+
+        sp = _ck._stream_ptr(stream, log_device)
+        with torch.cuda.device(dev):
+            check(lib().bkd_entrylog_scrub_report(
+                _ck._dev_ptr(log_device, "log"), log_size, ptr(d_off, "offsets", torch.int64),
+                ptr(d_len, "lengths", torch.int32), n, ptr(d_ids, "ledger ids", torch.int64),
+                ptr(d_types, "ledger types", torch.int32), ptr(d_keys, "ledger keys", torch.int32), len(table),
+                ptr(d_states, "key states", torch.int32) if table.nkeys else None, table.nkeys, mask,
+                ptr(d_status, "status"), _ck._dev_ptr(d_report, "report", torch.int64), ptr(d_bad, "bad list"), cap,
+                _ck._dev_ptr(d_nbad, "nbad", torch.int64), sp))
+            check(lib().bkd_stream_sync(sp))
+        nbad = int(d_nbad.cpu().numpy()[0])
+        listed = min(nbad, cap)
+        bad = d_bad[:listed].cpu().numpy().view(np.uint32) if listed else np.zeros(0, dtype=np.uint32)
+        status = d_status.cpu().numpy() if d_status is not None else None
+        return ScrubReport(scan, table, d_report.cpu().numpy().view(np.uint64), nbad, bad, log_host, status)
+
+    @staticmethod
+    def report_ledgers_host(log_host, table: LedgerTable, types=None, start: int = LOGFILE_HEADER_SIZE,
+                            max_bad: int = DEFAULT_MAX_BAD, want_status: bool = False):
+        """The same from host memory (``bkd_entrylog_scrub_report_host``), by the route ``verify_ledgers_host``
+        takes. Returns a ``ScrubReport``."""
+        scan = scan_entry_log(log_host, start)
+        n = len(scan)
+        buf = _ck._host_view(log_host)
+        cap = min(int(max_bad), n)
+        status = np.zeros(n, dtype=np.int32) if want_status else None
+        report = np.zeros((len(table) + 1) * REPORT_WORDS, dtype=np.uint64)
+        bad = np.zeros(cap, dtype=np.uint32)
+        nbad = ctypes.c_uint64(0)
+        check(lib().bkd_entrylog_scrub_report_host(
+            _ptr(buf), buf.size, _ptr(scan.offsets), _ptr(scan.lengths), n, _ptr(table.ids), _ptr(table.types),
+            _ptr(table.keys), len(table), _ptr(table.key_states), table.nkeys, _default_mask(table, types),
+            _ptr(status) if status is not None else None, _ptr(report), _ptr(bad), cap, ctypes.byref(nbad)))
+        return ScrubReport(scan, table, report, int(nbad.value), bad[:min(int(nbad.value), cap)], log_host, status)

@@ -542,6 +542,81 @@ BKD_API int bkd_entrylog_scrub_lanes(const void* d_log, uint64_t log_size, const
                                      uint64_t nledgers, const uint32_t* d_key_states, uint64_t nkeys,
                                      uint32_t types, uint32_t* d_lanes, uint32_t* d_nlanes, void* stream);
 
+/* Scrub report: bkd_entrylog_verify_ledgers, then what a scrub is read for, all on the device: one row per
+ * ledger and the ascending list of bad entries. Every input has the meaning it has in that call (the
+ * log, the index, the ledger table, the key table, `types`, `stream`); the statuses are that call's.
+ *
+ * d_status: n statuses as in that call, or NULL (they then live in the stream's scratch only).
+ * d_report: (nledgers + 1) x BKD_SCRUB_REPORT_WORDS uint64 words, row r for table row r. An entry that is in
+ *   range and at least 8 bytes long belongs to the row of its ledger id; an entry that is out of range,
+ *   shorter than 8 bytes or of a ledger the table does not list belongs to the last row. A ledger whose
+ *   type is masked out keeps its own row (its entries count in NOT_CHECKED). Words of a row:
+ *     BKD_REPORT_ENTRIES          entries of the row; == OK + BAD + NOT_CHECKED
+ *     BKD_REPORT_BYTES            sum of length + 4 over them, 64 bits wide: what EntryLogMetadata keeps per
+ *                                 ledger (DefaultEntryLogger.java:1191, readableBytes() + 4)
+ *     BKD_REPORT_OK / BAD / NOT_CHECKED   entries with status 0 / above 0 / BKD_VERIFY_NOT_CHECKED
+ *     BKD_REPORT_MIN_BAD_ENTRY / MAX_BAD_ENTRY   lowest / highest entry id (bytes [8, 16) big-endian, compared
+ *                                 as signed 64-bit values, stored as bits) of a bad entry that is in range
+ *                                 and at least 16 bytes long; INT64_MAX / INT64_MIN when there is none
+ *     BKD_REPORT_FIRST_BAD_INDEX  lowest index i of a bad entry of the row, n when there is none
+ * d_bad, bad_capacity, d_nbad: *d_nbad = the entries with a status above 0 (it may exceed the capacity);
+ *   d_bad[0, min(*d_nbad, bad_capacity)) = their indices ascending, so d_bad[0] is that call's first_bad and
+ *   a truncated list holds the lowest ones; nothing is written at or behind min(*d_nbad, bad_capacity).
+ *   bad_capacity == 0 with a NULL d_bad is legal.
+ * n == 0: the rows get their initial values (zeros, INT64_MAX, INT64_MIN, 0), *d_nbad = 0, nothing else
+ * is launched. nledgers == 0 is legal: the only row is the catch-all row.
+ *
+ * Device sequence (scrub_report_kernels.hpp): that call's kernels unchanged, then row init ->
+ * one lane per entry (lanes of a wave that share a row combine in the wave; one lane per row and wave issues
+ * the 64-bit atomics, one per block where all of a block's waves sit on one row) -> a one-block scan of the blocks' bad counts -> the bad indices scattered in lane
+ * order. Asynchronous on `stream`, no host synchronisation; the bounds flag is raised exactly as by that
+ * call. Argument errors: that call's, a null d_report or d_nbad, bad_capacity > 0 with a null d_bad. */
+#define BKD_SCRUB_REPORT_WORDS 8
+#define BKD_REPORT_ENTRIES 0
+#define BKD_REPORT_BYTES 1
+#define BKD_REPORT_OK 2
+#define BKD_REPORT_BAD 3
+#define BKD_REPORT_NOT_CHECKED 4
+#define BKD_REPORT_MIN_BAD_ENTRY 5
+#define BKD_REPORT_MAX_BAD_ENTRY 6
+#define BKD_REPORT_FIRST_BAD_INDEX 7
+BKD_API int bkd_entrylog_scrub_report(const void* d_log, uint64_t log_size, const uint64_t* d_offsets,
+                                      const uint32_t* d_lengths, uint64_t n, const int64_t* d_ledger_ids,
+                                      const uint32_t* d_ledger_types, const uint32_t* d_ledger_keys,
+                                      uint64_t nledgers, const uint32_t* d_key_states, uint64_t nkeys,
+                                      uint32_t types, int32_t* d_status, uint64_t* d_report, uint32_t* d_bad,
+                                      uint64_t bad_capacity, uint64_t* d_nbad, void* stream);
+/* Host-resident form: the arguments of bkd_entrylog_verify_ledgers_host with host outputs as above; h_status
+ * may be NULL. Synchronous. The table checks, the routes (bkd_get_scrub_host_route answers for this call too)
+ * and the rule that everything is written before BKD_ERR_BOUNDS is returned are that call's. Route 1: the CPU
+ * route's statuses, then one serial pass with the rules the device applies (scrub_report_rules.hpp); no
+ * device needed. Route 2: one upload, the device call on a stream of its own, then the report, the list and
+ * *h_nbad copied back, and the statuses only when h_status is given. */
+BKD_API int bkd_entrylog_scrub_report_host(const void* h_log, uint64_t log_size, const uint64_t* h_offsets,
+                                           const uint32_t* h_lengths, uint64_t n, const int64_t* h_ledger_ids,
+                                           const uint32_t* h_ledger_types, const uint32_t* h_ledger_keys,
+                                           uint64_t nledgers, const uint32_t* h_key_states, uint64_t nkeys,
+                                           uint32_t types, int32_t* h_status, uint64_t* h_report, uint32_t* h_bad,
+                                           uint64_t bad_capacity, uint64_t* h_nbad);
+/* The ledgers map of an entry log in a HOST buffer, read as getHeaderForLogId and
+ * extractEntryLogMetadataFromIndex do (DefaultEntryLogger.java:881-906, :1089-1176): the header's version
+ * (byte 4, int32 BE), ledgersMapOffset (byte 8, int64) and ledgersCount (byte 16, int32); from the offset,
+ * records [int32 size][int64 -1][int64 -2][int32 count][(int64 ledger, int64 size) x count] until a size
+ * <= 0 or the end of the buffer. Writes the pairs as they lie (duplicates included) to h_ledger_ids /
+ * h_sizes up to `capacity` (*h_count = the pairs found; BKD_ERR_BOUNDS when that is more than `capacity`, the
+ * first `capacity` of them written and the map checked all the same), the three header fields
+ * (each pointer may be NULL) and *h_state: BKD_LEDGERS_MAP_READ; BKD_LEDGERS_MAP_ABSENT (version < 1 or
+ * offset 0: the reference falls back to scanning); BKD_LEDGERS_MAP_MALFORMED wherever the reference throws,
+ * bkd_last_error naming the case: a record's ledger id != -1, its entry id != -2, a record longer or shorter
+ * than its count implies, a short read, distinct ledgers != the header's count, a header count of 0. The
+ * return value is BKD_OK for all three states. Host-only control logic: it computes no digest. */
+#define BKD_LEDGERS_MAP_READ 0
+#define BKD_LEDGERS_MAP_ABSENT 1
+#define BKD_LEDGERS_MAP_MALFORMED 2
+BKD_API int bkd_entrylog_ledgers_map(const void* h_log, uint64_t log_size, int64_t* h_ledger_ids, int64_t* h_sizes,
+                                     uint64_t capacity, uint64_t* h_count, int32_t* h_version,
+                                     int64_t* h_map_offset, int32_t* h_ledgers_count, int32_t* h_state);
+
 /* ---- MAC ledgers: batched HMAC-SHA1 (DigestType.MAC, MacDigestManager) ------------------
  * MacDigestManager ($BK/proto/checksum/MacDigestManager.java:46-107) digests with HmacSHA1 keyed with
  * SHA1("mac" || passwd) (:61, :79-84); the digest is 20 bytes (:67-69) written after the 32-byte header
