@@ -115,6 +115,10 @@ PROTOTYPES = {
     "bkd_digest_verify_requests_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "bkd_digest_package_batch_ledgers_mac_host": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp,
                                                          _u64]),
+    "bkd_digest_reframe_requests_mac": (_int, [_vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp,
+                                               _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bkd_digest_reframe_requests_mac_host": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp]),
     "bkd_digest_package_batch_segments_mac": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64,
                                                      _vp, _u64, _vp, _u64, _vp]),
     "bkd_digest_package_batch_v2_mac": (_int, [_vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp,

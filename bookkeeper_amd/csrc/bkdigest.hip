@@ -1816,12 +1816,13 @@ int mac_package_host_staged(const uint32_t* h_key_states, uint64_t nkeys, const 
                                bkd::host::kMacFrameHead, false, out);
 }
 
-// Read requests of MAC ledgers (bkd_digest_verify_requests_mac; rq as verify_framed takes it, keys.index
-// per request): the CSR expanded into the stream's verify scratch and checked and the prefixes initialised
-// by request_expand_kernel, then the verify kernel over bkd::MacRequests.
-int mac_verify_requests(DeviceState& ds, hipStream_t st, const MacKeys& keys, const void* d_framed, uint64_t size,
-                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, int32_t* d_status,
-                        const Requests& rq) {
+// Read requests of MAC ledgers (bkd_digest_verify_requests_mac, bkd_digest_reframe_requests_mac; rq as
+// verify_framed takes it, keys.index per request): the CSR expanded into the stream's verify scratch and
+// checked and the prefixes initialised by request_expand_kernel, then launch(who, err) enqueues the call's
+// kernel over bkd::MacRequests.
+template <class Launch>
+int mac_requests(DeviceState& ds, hipStream_t st, const MacKeys& keys, uint64_t n, const Requests& rq,
+                 const Launch& launch) {
     if (n == 0) {
         if (rq.nreq) BKD_HIP(hipMemsetAsync(rq.first_bad, 0, rq.nreq * sizeof(uint64_t), st));
         return BKD_OK;
@@ -1842,12 +1843,35 @@ int mac_verify_requests(DeviceState& ds, hipStream_t st, const MacKeys& keys, co
     hipLaunchKernelGGL(bkd::request_expand_kernel, dim3(xblocks), dim3(256), 0, st, rq.first, rq.nreq, n, rq.ledger_ids,
                        rq.first_entry_ids, rq.flags, xlid, xeid, req_of, (unsigned long long*)rq.first_bad, err);
     BKD_HIP(hipGetLastError());
-    const bkd::MacRequests who{keys.states, keys.nkeys, keys.index,
-                               bkd::RequestIds{xlid, xeid, req_of, rq.first, (unsigned long long*)rq.first_bad}};
-    hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacRequests>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
-                       (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
+    launch(bkd::MacRequests{keys.states, keys.nkeys, keys.index,
+                            bkd::RequestIds{xlid, xeid, req_of, rq.first, (unsigned long long*)rq.first_bad}},
+           err);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
+}
+
+int mac_verify_requests(DeviceState& ds, hipStream_t st, const MacKeys& keys, const void* d_framed, uint64_t size,
+                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, int32_t* d_status,
+                        const Requests& rq) {
+    return mac_requests(ds, st, keys, n, rq, [&](const bkd::MacRequests& who, uint32_t* err) {
+        hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacRequests>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                           (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
+    });
+}
+
+// The reframe kernel over n frames: in place, or apart into d_out_frames at `stride` (mac_kernels.hpp).
+template <class Who>
+void mac_reframe_launch(hipStream_t st, const Who& who, bool trusted, void* d_framed, uint64_t size,
+                        const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, const int64_t* d_new_lacs,
+                        void* d_out_frames, uint64_t stride, int32_t* d_status, uint32_t* err) {
+    if (trusted)
+        hipLaunchKernelGGL((bkd::mac_reframe_kernel<Who, true>), dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                           (uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_new_lacs, (uint8_t*)d_out_frames, stride,
+                           d_status, err);
+    else
+        hipLaunchKernelGGL((bkd::mac_reframe_kernel<Who, false>), dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
+                           (uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_new_lacs, (uint8_t*)d_out_frames, stride,
+                           d_status, err);
 }
 
 // The verify kernel over one staged segment of the host form: who holds the segment's expectations.
@@ -1859,6 +1883,19 @@ int mac_verify_expected(DeviceState& ds, hipStream_t st, const bkd::MacExpected&
     if (rc) return rc;
     hipLaunchKernelGGL(bkd::mac_verify_kernel<bkd::MacExpected>, dim3(mac_blocks(n)), dim3(bkd::kMacBlock), 0, st, who,
                        (const uint8_t*)d_framed, size, d_offsets, d_lengths, n, d_status, err);
+    BKD_HIP(hipGetLastError());
+    return BKD_OK;
+}
+
+// The reframe kernel over one staged segment of the host form: out-frames apart, packed at 52 bytes.
+int mac_reframe_expected(DeviceState& ds, hipStream_t st, const bkd::MacExpected& who, bool trusted, void* d_framed,
+                         uint64_t size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n,
+                         const int64_t* d_new_lacs, void* d_out_frames, int32_t* d_status) {
+    uint32_t* err = nullptr;
+    const int rc = bounds_flag(ds, st, &err);
+    if (rc) return rc;
+    mac_reframe_launch(st, who, trusted, d_framed, size, d_offsets, d_lengths, n, d_new_lacs, d_out_frames,
+                       bkd::host::kMacFrameHead, d_status, err);
     BKD_HIP(hipGetLastError());
     return BKD_OK;
 }
@@ -1882,12 +1919,18 @@ int mac_host_route(const uint32_t* lengths, uint64_t n) {
 
 // One staged segment's expectations, as verify_requests_host has put them on the device: a ledger id, an
 // entry id and a flag word (bkd::host::kSkipEntryId or 0) per entry, then one zero u64 on an 8-byte boundary.
-// req_of: the host's request index | skip bit of the segment's entries.
+// req_of: the host's request index | skip bit of the segment's entries; first: the call's index of entry 0.
 struct StagedRequests {
     const int64_t *d_lid, *d_eid;
     const uint32_t* d_flag;
     const uint64_t* d_zero;
     const uint32_t* req_of;
+    uint64_t first;
+};
+
+// What a verify form has left to do with a drained segment: nothing.
+struct NothingDrained {
+    int operator()(HostStage&, int, uint64_t, uint64_t) const { return BKD_OK; }
 };
 
 // bkd_digest_verify_requests_host and bkd_digest_verify_requests_mac_host. Checked before any work, in this
@@ -1898,12 +1941,15 @@ struct StagedRequests {
 // host on either route, so a request that straddles two staged segments gets the minimum over both parts.
 // host(xlid, xeid, req_of) returns the form's route (< 0: its error) and, where that is 1, has verified every
 // frame on the CPU. launch(ds, hs, s, cnt, bytes, x) enqueues the verify sequence over slot s's staged frames
-// and expectations x, statuses to d_res. init...: the StagedCall groups the launch needs.
-template <class Host, class Launch, class... Init>
+// and expectations x, statuses to d_res. drained(hs, s, i0, cnt): the segment's statuses are in h_status and
+// whatever else the launch had copied back is in slot s (the MAC reframe's out-frames). init...: the
+// StagedCall groups the launch needs.
+template <class Host, class Launch, class Drained, class... Init>
 int verify_requests_host(const MacKeys* keys, const void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
                          const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
                          const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags, int32_t* h_status,
-                         uint64_t* h_req_first_bad, const Host& host, const Launch& launch, Init... init) {
+                         uint64_t* h_req_first_bad, const Host& host, const Launch& launch, const Drained& drained,
+                         Init... init) {
     if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
     if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
     if ((keys && !keys->index) || !h_req_first || !h_req_ledger_ids || !h_req_first_entry_ids || !h_req_flags ||
@@ -1958,14 +2004,14 @@ int verify_requests_host(const MacKeys* keys, const void* const* h_frames, const
         r = launch(*call.ds, hs, s, cnt, bytes,
                    StagedRequests{reinterpret_cast<const int64_t*>(d), reinterpret_cast<const int64_t*>(d + o_eid),
                                   reinterpret_cast<const uint32_t*>(d + o_flag),
-                                  reinterpret_cast<const uint64_t*>(d + o_zero), req_of.data() + i0});
+                                  reinterpret_cast<const uint64_t*>(d + o_zero), req_of.data() + i0, i0});
         if (r) return r;
         BKD_HIP(hipMemcpyAsync(hs.h_res[s], hs.d_res[s], cnt * 4, hipMemcpyDeviceToHost, st));
         return BKD_OK;
     };
     auto drain = [&](int s, uint64_t i0, uint64_t cnt) -> int {
         memcpy(h_status + i0, hs.h_res[s], cnt * 4);
-        return BKD_OK;
+        return drained(hs, s, i0, cnt);
     };
     const int rc = host_segments(hs, h_lengths, n, HostStage::kSegEntries, seg, drain);
     if (rc == BKD_OK) prefixes();
@@ -2900,7 +2946,7 @@ int bkd_digest_verify_requests_host(int algo, const void* const* h_frames, const
             return verify_framed(ds, hs.st[s], algo, 0, 0, 0, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
                                  reinterpret_cast<int32_t*>(hs.d_res[s]), nullptr, &rq);
         },
-        &HostStage::init_verify, &HostStage::init_requests);
+        NothingDrained{}, &HostStage::init_verify, &HostStage::init_requests);
 }
 
 int bkd_digest_package_batch_ledgers_host(int algo, const int64_t* h_ledger_ids, const int64_t* h_entry_ids,
@@ -3225,7 +3271,90 @@ int bkd_digest_verify_requests_mac_host(const uint32_t* h_key_states, uint64_t n
                                        hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt,
                                        reinterpret_cast<int32_t*>(hs.d_res[s]));
         },
-        &HostStage::init_requests);
+        NothingDrained{}, &HostStage::init_requests);
+}
+
+int bkd_digest_reframe_requests_mac(const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_req_keys,
+                                    uint32_t flags, void* d_framed, uint64_t framed_size, const uint64_t* d_offsets,
+                                    const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first, uint64_t nreq,
+                                    const int64_t* d_req_ledger_ids, const int64_t* d_req_first_entry_ids,
+                                    const uint32_t* d_req_flags, const int64_t* d_new_lacs, void* d_out_frames,
+                                    uint64_t frame_stride, int32_t* d_status, uint64_t* d_req_first_bad, void* stream) {
+    if (flags & ~BKD_REFRAME_TRUSTED) return fail(BKD_ERR_INVALID_ARG, "unknown reframe flags");
+    if (nreq >= 0x80000000ull) return fail(BKD_ERR_INVALID_ARG, "a call holds fewer than 2^31 requests");
+    if (d_out_frames) {
+        if (int rc = check_frame_stride(bkd::host::kMacFrameHead, frame_stride, false)) return rc;
+    } else if (frame_stride != 0) {
+        return fail(BKD_ERR_INVALID_ARG, "a frame stride without out_frames");
+    }
+    if (nreq == 0) return n ? fail(BKD_ERR_INVALID_ARG, "entries without a request") : BKD_OK;
+    if (!d_req_keys || !d_req_first || !d_req_ledger_ids || !d_req_first_entry_ids || !d_req_flags || !d_req_first_bad)
+        return fail(BKD_ERR_INVALID_ARG, "null request array");
+    if (nkeys && !d_key_states) return fail(BKD_ERR_INVALID_ARG, "null key table");
+    if (n && (!d_offsets || !d_lengths || !d_status)) return fail(BKD_ERR_INVALID_ARG, "null buffer");
+    if (n && !d_framed) return fail(BKD_ERR_INVALID_ARG, "null framed buffer");
+    if (n && !d_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
+    if (n > kMacMaxBatch) return fail(BKD_ERR_INVALID_ARG, "batch too large");
+    if (n && d_out_frames) {
+        const uint64_t fr0 = (uint64_t)(uintptr_t)d_out_frames, fr1 = fr0 + (n - 1u) * frame_stride + bkd::host::kMacFrameHead;
+        const uint64_t in0 = (uint64_t)(uintptr_t)d_framed, in1 = in0 + framed_size;
+        if (fr0 < in1 && in0 < fr1) return fail(BKD_ERR_INVALID_ARG, "out_frames overlaps the framed buffer");
+    }
+    Call call(stream);
+    if (call.rc) return call.rc;
+    const Requests rq{nreq, d_req_first, d_req_ledger_ids, d_req_first_entry_ids, d_req_flags, d_req_first_bad};
+    const hipStream_t st = call.st;
+    return mac_requests(*call.ds, st, MacKeys{d_key_states, nkeys, d_req_keys}, n, rq,
+                        [&](const bkd::MacRequests& who, uint32_t* err) {
+                            mac_reframe_launch(st, who, (flags & BKD_REFRAME_TRUSTED) != 0, d_framed, framed_size, d_offsets,
+                                               d_lengths, n, d_new_lacs, d_out_frames, frame_stride, d_status, err);
+                        });
+}
+
+int bkd_digest_reframe_requests_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_req_keys,
+                                         uint32_t flags, void* const* h_frames, const uint32_t* h_lengths, uint64_t n,
+                                         const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
+                                         const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags,
+                                         const int64_t* h_new_lacs, int32_t* h_status, uint64_t* h_req_first_bad) {
+    if (flags & ~BKD_REFRAME_TRUSTED) return fail(BKD_ERR_INVALID_ARG, "unknown reframe flags");
+    if (n && !h_new_lacs) return fail(BKD_ERR_INVALID_ARG, "null new_lacs");
+    const bool trusted = (flags & BKD_REFRAME_TRUSTED) != 0;
+    const MacKeys keys{h_key_states, nkeys, h_req_keys};
+    DeviceTable table;  // uploaded once, by the first segment (the staged call has entered the device by then)
+    constexpr uint64_t hl = bkd::host::kMacFrameHead;
+    return verify_requests_host(
+        &keys, h_frames, h_lengths, n, h_req_first, nreq, h_req_ledger_ids, h_req_first_entry_ids, h_req_flags, h_status,
+        h_req_first_bad,
+        [&](const int64_t* xlid, const int64_t* xeid, const uint32_t* req_of) {
+            const int route = mac_host_route(h_lengths, n);
+            if (route == 1)
+                bkd::host::mac_reframe_frames_expected(h_key_states, h_req_keys, xlid, xeid, req_of, trusted,
+                                                       (uint8_t* const*)h_frames, h_lengths, n, h_new_lacs, h_status);
+            return route;
+        },
+        // staged as verify with the new LACs beside; the device leaves its copy of the frames alone and writes
+        // packed 52-byte out-frames, which come back with the statuses
+        [&](DeviceState& ds, HostStage& hs, int s, uint64_t cnt, uint64_t bytes, const StagedRequests& x) -> int {
+            if (int rc = table.upload(h_key_states, nkeys)) return rc;
+            const hipStream_t st = hs.st[s];
+            for (uint64_t j = 0; j < cnt; ++j) hs.h_seed[s][j] = h_req_keys[x.req_of[j] & ~bkd::host::kSkipEntryId];
+            BKD_HIP(hipMemcpyAsync(hs.d_seed[s], hs.h_seed[s], cnt * 4, hipMemcpyHostToDevice, st));
+            memcpy(hs.h_lac[s], h_new_lacs + x.first, cnt * 8);
+            BKD_HIP(hipMemcpyAsync(hs.d_lac[s], hs.h_lac[s], cnt * 8, hipMemcpyHostToDevice, st));
+            const int rc = mac_reframe_expected(ds, st, bkd::MacExpected{table.d, nkeys, hs.d_seed[s], x.d_lid, x.d_eid, x.d_flag},
+                                                trusted, hs.d_buf[s], bytes, hs.d_off[s], hs.d_len[s], cnt, hs.d_lac[s],
+                                                hs.d_frm[s], reinterpret_cast<int32_t*>(hs.d_res[s]));
+            if (rc) return rc;
+            BKD_HIP(hipMemcpyAsync(hs.h_frm[s], hs.d_frm[s], cnt * hl, hipMemcpyDeviceToHost, st));
+            return BKD_OK;
+        },
+        // the host writes bytes 16..23 and 32..51 of each OK frame
+        [&](HostStage& hs, int s, uint64_t i0, uint64_t cnt) -> int {
+            bkd::host::mac_apply_reframe((uint8_t* const*)h_frames + i0, cnt, hs.h_frm[s],
+                                         reinterpret_cast<const int32_t*>(hs.h_res[s]));
+            return BKD_OK;
+        },
+        &HostStage::init_requests, &HostStage::init_reframe, &HostStage::init_package);
 }
 
 int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_key_of,

@@ -188,6 +188,98 @@ void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_
     });
 }
 
+// ---- re-framing with a new LAC ----
+
+namespace {
+
+// Block `pos` of the padded message pre[0, 32) || p[0, len) as hash_message builds it: read in place where
+// it lies whole inside p, else put together from the message's own bytes and padded. (hash_message keeps
+// its own loop: how it falls in a cache line is measured, see above, and the package and verify routes are
+// to stay the machine code they were.)
+inline void frame_block(uint32_t (&w)[16], const uint8_t* pre, const uint8_t* p, uint64_t pos, uint64_t m,
+                        uint64_t padded, uint64_t bits) {
+    if (pos >= 32u && pos + 64u <= m) {
+        const uint8_t* q = p + (pos - 32u);
+        for (int t = 0; t < 16; ++t) w[t] = be32(q + 4 * t);
+        return;
+    }
+    uint8_t buf[64] = {0};
+    const uint64_t end = std::min(pos + 64u, m);
+    if (pos < 32u) memcpy(buf, pre + pos, (size_t)(std::min<uint64_t>(end, 32u) - pos));
+    const uint64_t d0 = std::max<uint64_t>(pos, 32u);
+    if (end > d0) memcpy(buf + (d0 - pos), p + (d0 - 32u), (size_t)(end - d0));
+    for (int t = 0; t < 16; ++t) w[t] = sha1::padded_word(be32(buf + 4 * t), pos + 4u * t, m, padded, bits);
+}
+
+// mac_v / mac_n = HMAC over pre_v / pre_n (32 bytes each) || p[0, len): block 0 per header, every later
+// block expanded once for both chains (sha1::compress2), as the device's mac_entry2.
+void mac_two_headers(const uint32_t* key_state, const uint8_t* pre_v, const uint8_t* pre_n, const uint8_t* p,
+                     uint64_t len, uint8_t* mac_v, uint8_t* mac_n) {
+    const uint64_t m = 32u + len;
+    const uint64_t padded = sha1::padded_bytes(m);
+    const uint64_t bits = sha1::hmac_inner_bits(m);
+    uint32_t hv[5], hn[5], w[16], ov[5], on[5];
+    for (int k = 0; k < 5; ++k) hv[k] = hn[k] = key_state[k];
+    frame_block(w, pre_v, p, 0, m, padded, bits);
+    sha1::compress(hv, w);
+    frame_block(w, pre_n, p, 0, m, padded, bits);
+    sha1::compress(hn, w);
+    for (uint64_t pos = 64u; pos < padded; pos += 64u) {
+        frame_block(w, pre_v, p, pos, m, padded, bits);
+        sha1::compress2(hv, hn, w);
+    }
+    sha1::hmac_outer(key_state + 5, hv, ov);
+    sha1::hmac_outer(key_state + 5, hn, on);
+    for (int k = 0; k < 5; ++k) {
+        put_be32(mac_v + 4 * k, ov[k]);
+        put_be32(mac_n + 4 * k, on[k]);
+    }
+}
+
+// One frame, as the device's mac_reframe_kernel: the status of mac_verify_one (trusted: what the header
+// alone decides, never 2), bytes 16..23 and 32..51 rewritten where it is 0.
+int32_t mac_reframe_one(const uint32_t* key_state, uint8_t* f, uint32_t l, int64_t ledger_id, int64_t entry_id,
+                        bool skip_entry_id, bool trusted, int64_t new_lac) {
+    if (l < kMacFrameHead) return 1;
+    uint8_t hdr[32], mac_v[kMacLen], mac_n[kMacLen];
+    memcpy(hdr, f, 32);
+    put_be64(hdr + 16, (uint64_t)new_lac);
+    const int64_t lid = (int64_t)(((uint64_t)be32(f) << 32) | be32(f + 4));
+    const int64_t eid = (int64_t)(((uint64_t)be32(f + 8) << 32) | be32(f + 12));
+    if (trusted) {
+        mac_one(key_state, hdr, 32, f + kMacFrameHead, l - kMacFrameHead, mac_n);
+    } else {
+        mac_two_headers(key_state, f, hdr, f + kMacFrameHead, l - kMacFrameHead, mac_v, mac_n);
+        if (memcmp(mac_v, f + 32, kMacLen) != 0) return 2;
+    }
+    if (lid != ledger_id) return 3;
+    if (!skip_entry_id && eid != entry_id) return 4;
+    memcpy(f + 16, hdr + 16, 8);
+    memcpy(f + 32, mac_n, kMacLen);
+    return 0;
+}
+
+}  // namespace
+
+void mac_reframe_frames_expected(const uint32_t* key_states, const uint32_t* req_keys, const int64_t* ledger_ids,
+                                 const int64_t* entry_ids, const uint32_t* req_of, bool trusted, uint8_t* const* frames,
+                                 const uint32_t* lens, uint64_t n, const int64_t* new_lacs, int32_t* status) {
+    each_entry(n, lens, [&](uint64_t i) {
+        const uint32_t* key = key_states + (uint64_t)req_keys[req_of[i] & ~kSkipEntryId] * 10u;
+        status[i] = mac_reframe_one(key, frames[i], lens[i], ledger_ids[i], entry_ids[i], (req_of[i] & kSkipEntryId) != 0,
+                                    trusted, new_lacs[i]);
+    });
+}
+
+void mac_apply_reframe(uint8_t* const* frames, uint64_t n, const uint8_t* out_frames, const int32_t* status) {
+    for (uint64_t i = 0; i < n; ++i) {
+        if (status[i] != 0) continue;
+        const uint8_t* o = out_frames + i * kMacFrameHead;
+        memcpy(frames[i] + 16, o + 16, 8);
+        memcpy(frames[i] + 32, o + 32, kMacLen);
+    }
+}
+
 // ---- composite entries and V2 add requests ----
 
 namespace {

@@ -46,6 +46,18 @@ void mac_package_frames_ledgers(const uint32_t* key_states, const uint32_t* key_
                                 const uint8_t* const* payloads, const uint32_t* lens, uint64_t n, uint8_t* frames,
                                 uint64_t stride);
 
+// Re-framing with a new LAC (bkd_digest_reframe_requests_mac_host): frame i, a writable buffer, checked as
+// mac_verify_frames_expected checks it and, where its status is 0, rewritten in place for new_lacs[i]: header
+// bytes 16..23 and the MAC at 32..51. One pass over the payload: every block behind the first is expanded
+// once and compressed into both chains (sha1::compress2). trusted: one chain under the new header, the
+// status what the header alone decides (never 2) — the MAC is valid for the bytes as they lie.
+void mac_reframe_frames_expected(const uint32_t* key_states, const uint32_t* req_keys, const int64_t* ledger_ids,
+                                 const int64_t* entry_ids, const uint32_t* req_of, bool trusted, uint8_t* const* frames,
+                                 const uint32_t* lens, uint64_t n, const int64_t* new_lacs, int32_t* status);
+// The GPU route's last step: bytes 16..23 and 32..51 of the packed 52-byte out-frame i into frames[i],
+// where status[i] is 0.
+void mac_apply_reframe(uint8_t* const* frames, uint64_t n, const uint8_t* out_frames, const int32_t* status);
+
 // Composite entries and V2 add requests (bkd_digest_package_batch_segments_mac_host,
 // bkd_digest_package_batch_v2_mac_host). key_of (may be null: row 0 for all) and ledger_ids (may be null:
 // ledger_id for all) as above.

@@ -588,4 +588,151 @@ __global__ void __launch_bounds__(kMacBlock) mac_verify_kernel(
     if (st != 0) x.failed(i);
 }
 
+// ---- re-framing with a new LAC (bkd_digest_reframe_requests_mac) -------------------------------------
+// HMAC has no algebra that carries a digest from one header to another (the CRC reframe's GF(2)
+// correction), so a MAC reframe hashes again. The old and the new frame differ only in header bytes
+// 16..23, words 4 and 5 of the first block; every later block of the inner hash holds the same words for
+// both. mac_entry2 therefore walks the stream once — one set of loads, one v_perm_b32 per word, one
+// schedule expansion per block — and runs two round chains on it (sha1::compress2): chain V from the
+// header as it lies, chain N from the header with the new LAC. Block 0 and the outer hashes differ in their
+// words and are compressed per chain.
+template <class Key>
+__device__ __forceinline__ void mac_entry2(const Key& key, const uint32_t (&pre)[8], uint32_t lac_hi, uint32_t lac_lo,
+                                           const MacStream& in, uint32_t k0, uint32_t len, uint32_t (&mac_v)[5],
+                                           uint32_t (&mac_n)[5]) {
+    const uint64_t m = (uint64_t)len + 32u;
+    const uint64_t padded = sha1::padded_bytes(m);
+    const uint64_t bits = sha1::hmac_inner_bits(m);
+    uint32_t hv[5], hn[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) hv[k] = hn[k] = key.inner()[k];
+    uint32_t edge;  // the dword the next block's first word starts in
+    {
+        uint32_t first[1];
+        in.load<1>(k0, first);
+        edge = first[0];
+    }
+    ++k0;
+    {  // block 0: the header and the first 32 bytes of the stream, once per header
+        uint32_t d[8], w[16], w2[16];
+        in.load<8>(k0, d);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) w[t] = pre[t];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) w[8 + t] = in.word(t == 0 ? edge : d[t - 1], d[t]);
+        if (m < 64u) {
+#pragma unroll
+            for (int t = 8; t < 16; ++t) w[t] = sha1::padded_word(w[t], 4u * t, m, padded, bits);
+        }
+#pragma unroll
+        for (int t = 0; t < 16; ++t) w2[t] = w[t];
+        w2[4] = lac_hi;
+        w2[5] = lac_lo;
+        sha1::compress(hv, w);
+        sha1::compress(hn, w2);
+        edge = d[7];
+        k0 += 8u;
+    }
+    uint64_t pos = 64u;
+    if (pos < padded) {
+        uint32_t d[16];
+        in.load<16>(k0, d);
+        for (;;) {
+            uint32_t w[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) w[t] = in.word(t == 0 ? edge : d[t - 1], d[t]);
+            edge = d[15];
+            k0 += 16u;
+            const bool last = pos + 64u >= padded;
+            if (!last) in.load<16>(k0, d);  // block k + 1's loads in flight during block k's rounds
+            if (pos + 64u > m) {
+#pragma unroll
+                for (int t = 0; t < 16; ++t) w[t] = sha1::padded_word(w[t], pos + 4u * t, m, padded, bits);
+            }
+            sha1::compress2(hv, hn, w);
+            if (last) break;
+            pos += 64u;
+        }
+    }
+    sha1::hmac_outer(key.outer(), hv, mac_v);
+    sha1::hmac_outer(key.outer(), hn, mac_n);
+}
+
+// Frame i as mac_verify_kernel reads it, re-framed with new_lacs[i] where its status is 0.
+//
+// Default (TRUSTED == false): status, precedence, the verified-prefix word of `who` and the bounds flag are
+// those of mac_verify_kernel<Who> on the same input; the MAC under the new header comes from the same pass
+// (mac_entry2) and is written only for status 0.
+// TRUSTED: the caller has verified the frames. One chain (mac_entry<true>, the new header as prefix); the
+// status is what the header alone decides — 1 too short, unreadable or no key row, else the policy's
+// id_status — never 2. Unlike the CRC trusted reframe, which carries a wrong digest over into a digest
+// that is wrong again, the MAC written here is valid for the bytes as they lie: a frame whose payload was
+// damaged comes out verifying. The caller vouches for the bytes.
+//
+// Output, status 0 only; no byte of any other frame or out-frame is written.
+//   apart (out_frames != null): [32 B header with the new LAC][20 B MAC] at out_frames + i * stride.
+//   in place: bytes 16..23 and 32..51 of the frame itself.
+// Frames start at any byte address and may lie back to back, so a lane's aligned edge dwords can hold bytes
+// of a neighbour's frame that the neighbour's lane rewrites in this launch. The loads do not mind: bytes
+// outside the frame never reach the hash. The stores never read-modify-write: store_be_words writes whole
+// dwords only where the range is 4-byte aligned (its dwords then lie inside it) and single bytes otherwise.
+// The lane holds bytes [0, 52) in registers before its first store (the status depends on them).
+template <class Who, bool TRUSTED>
+__global__ void __launch_bounds__(kMacBlock) mac_reframe_kernel(
+    Who who, uint8_t* framed, uint64_t size, const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ lengths,
+    uint64_t n, const int64_t* __restrict__ new_lacs, uint8_t* out_frames, uint64_t stride,
+    int32_t* __restrict__ status, uint32_t* __restrict__ err) {
+    const uint64_t i = (uint64_t)blockIdx.x * kMacBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = offsets[i];
+    const uint32_t l = lengths[i];
+    const auto x = who.entry(i);
+    int32_t st;
+    if (!x.keyed() || !mac_readable(o, l, size)) {
+        st = 1;
+        atomicOr(err, 1u);
+    } else if (l < 52u) {
+        st = 1;
+    } else {
+        const MacStream in(framed + o, l);
+        const uint64_t lac = (uint64_t)new_lacs[i];
+        uint32_t d[14], hw[13];  // bytes [0, 52), as mac_verify_kernel holds them
+        in.load<14>(0u, d);
+#pragma unroll
+        for (int t = 0; t < 13; ++t) hw[t] = in.word(d[t], d[t + 1]);
+        uint32_t hdr[8], mac[5];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) hdr[t] = hw[t];
+        if (TRUSTED) {
+            hdr[4] = (uint32_t)(lac >> 32);
+            hdr[5] = (uint32_t)lac;
+            mac_entry<true>(x.key(), hdr, in, 13u, l - 52u, mac);
+            st = x.id_status(hw, i);
+        } else {
+            uint32_t old[5];
+            mac_entry2(x.key(), hdr, (uint32_t)(lac >> 32), (uint32_t)lac, in, 13u, l - 52u, old, mac);
+            uint32_t diff = 0u;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) diff |= old[k] ^ hw[8 + k];
+            st = diff ? 2 : x.id_status(hw, i);
+            hdr[4] = (uint32_t)(lac >> 32);
+            hdr[5] = (uint32_t)lac;
+        }
+        if (st == 0) {
+            if (out_frames) {
+                uint8_t* f = out_frames + i * stride;
+                store_be_words(f, hdr);
+                store_be_words(f + 32, mac);
+            } else {
+                uint8_t* f = framed + o;
+                const uint32_t lw[2] = {hdr[4], hdr[5]};
+                store_be_words(f + 16, lw);
+                store_be_words(f + 32, mac);
+            }
+        }
+    }
+    status[i] = st;
+    if (st != 0) x.failed(i);
+}
+
 }  // namespace bkd

@@ -82,6 +82,68 @@ BKD_HD void compress(uint32_t (&h)[5], uint32_t (&w)[16]) {
     h[4] += e;
 }
 
+// One block into two states: the block's words are the same for both (a reframe hashes every block behind
+// the first under the old and under the new header, HMAC's inner states differing from block 0 on), so the
+// schedule window w is expanded once and feeds two round chains, which are independent of each other and
+// interleave. w is clobbered as in compress.
+BKD_HD void compress2(uint32_t (&hA)[5], uint32_t (&hB)[5], uint32_t (&w)[16]) {
+    uint32_t a = hA[0], b = hA[1], c = hA[2], d = hA[3], e = hA[4];
+    uint32_t p = hB[0], q = hB[1], r = hB[2], s = hB[3], u = hB[4];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int t = 0; t < 80; ++t) {
+        uint32_t x;
+        if (t < 16) {
+            x = w[t];
+        } else {
+            x = rol(xor3(w[(t + 13) & 15], w[(t + 8) & 15], w[(t + 2) & 15]) ^ w[t & 15], 1);
+            w[t & 15] = x;
+        }
+        uint32_t f, g, k;
+        if (t < 20) {
+            f = bitsel(b, c, d);
+            g = bitsel(q, r, s);
+            k = 0x5A827999u;
+        } else if (t < 40) {
+            f = xor3(b, c, d);
+            g = xor3(q, r, s);
+            k = 0x6ED9EBA1u;
+        } else if (t < 60) {
+            f = maj(b, c, d);
+            g = maj(q, r, s);
+            k = 0x8F1BBCDCu;
+        } else {
+            f = xor3(b, c, d);
+            g = xor3(q, r, s);
+            k = 0xCA62C1D6u;
+        }
+        const uint32_t kx = k + x;  // shared by the two chains
+        const uint32_t tmpA = rol(a, 5) + f + (e + kx);
+        const uint32_t tmpB = rol(p, 5) + g + (u + kx);
+        e = d;
+        d = c;
+        c = rol(b, 30);
+        b = a;
+        a = tmpA;
+        u = s;
+        s = r;
+        r = rol(q, 30);
+        q = p;
+        p = tmpB;
+    }
+    hA[0] += a;
+    hA[1] += b;
+    hA[2] += c;
+    hA[3] += d;
+    hA[4] += e;
+    hB[0] += p;
+    hB[1] += q;
+    hB[2] += r;
+    hB[3] += s;
+    hB[4] += u;
+}
+
 // Bytes of a message of m bytes once padded (0x80, zeros, the 8-byte bit length): a multiple of 64.
 BKD_HD uint64_t padded_bytes(uint64_t m) { return (m + 9u + 63u) & ~(uint64_t)63; }
 

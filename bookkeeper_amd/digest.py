@@ -433,7 +433,10 @@ def _check_csr_sizes(nreq: int, *arrays) -> None:
 # of the per-entry arrays ((algo[, ledger id]) for CRC, ([ledger id]) for MAC), and `keys` the MAC forms' key
 # table, marshalled in front of those: (key_states, the index array, its name), None for CRC.
 
-def _verify_requests(fn, first, keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags, stream):
+def _verify_requests(fn, first, keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, skip_flags, stream,
+                     reframe=None):
+    """`reframe`: (new_lacs, out_frames or None, frame stride) of the reframe forms, marshalled behind the skip
+    flags."""
     import torch
     n = offsets.numel()
     dev = framed.device
@@ -453,8 +456,11 @@ def _verify_requests(fn, first, keys, framed, offsets, lengths, req_first, ledge
             framed.numel() * framed.element_size(), _ck._dev_ptr(offsets, "offsets", i64, dev),
             _ck._dev_ptr(lengths, "lengths", u32, dev, n), n, _ck._dev_ptr(req_first, "req_first", i64, dev), nreq,
             _ck._dev_ptr(ledger_ids, "ledger_ids", i64, dev), _ck._dev_ptr(first_entry_ids, "first_entry_ids", i64, dev),
-            _ck._dev_ptr(skip_flags, "skip_flags", u32, dev), _ck._dev_ptr(status, "status"),
-            _ck._dev_ptr(req_first_bad, "req_first_bad"), _ck._stream_ptr(stream, framed)))
+            _ck._dev_ptr(skip_flags, "skip_flags", u32, dev),
+            *((_ck._dev_ptr(reframe[0], "new_lacs", i64, dev, n),
+               None if reframe[1] is None else _ck._dev_ptr(reframe[1], "out_frames", torch.uint8, dev), reframe[2])
+              if reframe else ()),
+            _ck._dev_ptr(status, "status"), _ck._dev_ptr(req_first_bad, "req_first_bad"), _ck._stream_ptr(stream, framed)))
     return status, req_first_bad
 
 
@@ -480,9 +486,18 @@ def package_batch_ledgers(digest_type, ledger_ids, entry_ids, lacs, length_field
                            length_fields, payload, offsets, lengths, frame_stride, None, stream, sync_check)
 
 
-def _verify_requests_host(fn, first, keys, frames, req_first, ledger_ids, first_entry_ids, skip_flags):
+def _verify_requests_host(fn, first, keys, frames, req_first, ledger_ids, first_entry_ids, skip_flags, new_lacs=None):
+    """`new_lacs`: the reframe forms' LACs, one per frame, marshalled behind the skip flags; the frames are then
+    written and must be writable contiguous buffers."""
+    if new_lacs is not None and any(isinstance(f, np.ndarray) and not f.flags.c_contiguous for f in frames):
+        raise TypeError("frames must be contiguous: they are re-framed in place")
     views, ptrs, lens = _ck._host_entries(frames)
+    if new_lacs is not None and any(not v.flags.writeable for v in views):
+        raise TypeError("frames must be writable buffers: they are re-framed in place")
     n = len(views)
+    lacs = None if new_lacs is None else np.ascontiguousarray(new_lacs, dtype=np.int64)
+    if lacs is not None and lacs.size != n:
+        raise ValueError("new_lacs must have one element per frame")
     first_of = np.ascontiguousarray(req_first, dtype=np.uint64)
     if first_of.size < 1:
         raise ValueError("req_first holds nreq + 1 values")
@@ -497,7 +512,8 @@ def _verify_requests_host(fn, first, keys, frames, req_first, ledger_ids, first_
     vp = ctypes.c_void_p
     check(getattr(lib(), fn)(
         *table, *first, vp(ptrs.ctypes.data), vp(lens.ctypes.data), n, vp(first_of.ctypes.data), nreq, vp(lids.ctypes.data),
-        vp(eids.ctypes.data), vp(flags.ctypes.data), vp(status.ctypes.data), vp(first_bad.ctypes.data)))
+        vp(eids.ctypes.data), vp(flags.ctypes.data), *(() if lacs is None else (vp(lacs.ctypes.data),)),
+        vp(status.ctypes.data), vp(first_bad.ctypes.data)))
     del views
     return status, first_bad
 
@@ -590,6 +606,38 @@ def verify_requests_mac_host(key_states, req_keys, frames, req_first, ledger_ids
     work. Returns (status int32[n], req_first_bad uint64[nreq])."""
     return _verify_requests_host("bkd_digest_verify_requests_mac_host", (), (key_states, req_keys, "req_keys"), frames,
                                  req_first, ledger_ids, first_entry_ids, skip_flags)
+
+
+def reframe_requests_mac(key_states, req_keys, framed, offsets, lengths, req_first, ledger_ids, first_entry_ids, new_lacs,
+                         skip_flags=None, *, out_frames=None, frame_stride=None, trusted: bool = False, stream=None):
+    """Re-replication of MAC ledgers in one pass (bkd_digest_reframe_requests_mac): the requests, keys, statuses
+    and prefixes of ``verify_requests_mac``, and every frame whose status is 0 re-framed with new_lacs[i]
+    (int64[n]) — in place (header bytes 16..23 and the MAC at 32..51 of `framed`), or, with `out_frames` (a
+    uint8 device tensor of n strides of `frame_stride` >= 52 bytes, default 52), as [32 B header][20 B MAC] at
+    out_frames + i * frame_stride, `framed` left alone. No byte of a frame that is not OK is written.
+    ``trusted``: the caller has verified the frames; only the new MAC is computed and the status is what the
+    header alone decides (never 2) — the MAC written is valid for the bytes as they lie.
+    Returns (status int32[n], req_first_bad int64[nreq])."""
+    n = offsets.numel()
+    if out_frames is not None and frame_stride is None:
+        frame_stride = METADATA_LENGTH + MAC_LENGTH
+    stride = frame_stride or 0
+    if (out_frames is not None and n and stride >= METADATA_LENGTH + MAC_LENGTH and
+            out_frames.numel() * out_frames.element_size() < (n - 1) * stride + METADATA_LENGTH + MAC_LENGTH):
+        raise ValueError("out_frames is too small for n frames at this stride")
+    return _verify_requests("bkd_digest_reframe_requests_mac", (REFRAME_TRUSTED if trusted else 0,),
+                            (key_states, req_keys, "req_keys"), framed, offsets, lengths, req_first, ledger_ids,
+                            first_entry_ids, skip_flags, stream, reframe=(new_lacs, out_frames, stride))
+
+
+def reframe_requests_mac_host(key_states, req_keys, frames, req_first, ledger_ids, first_entry_ids, new_lacs,
+                              skip_flags=None, *, trusted: bool = False):
+    """``reframe_requests_mac`` for entries in host memory: `frames` is a sequence of writable contiguous host
+    buffers (bytearray, writable numpy arrays), each one framed entry, re-framed in place where its status is
+    0. Returns (status int32[n], req_first_bad uint64[nreq])."""
+    return _verify_requests_host("bkd_digest_reframe_requests_mac_host", (REFRAME_TRUSTED if trusted else 0,),
+                                 (key_states, req_keys, "req_keys"), frames, req_first, ledger_ids, first_entry_ids,
+                                 skip_flags, new_lacs=new_lacs)
 
 
 def package_batch_ledgers_mac_host(key_states, key_of, ledger_ids, entry_ids, lacs, length_fields, payloads,
@@ -1026,10 +1074,9 @@ class MacDigestManager(DigestManager):
 
     def _no_batch(self, *a, **k):
         raise NotImplementedError(
-            "MAC ledgers have package_batch / verify_batch and their _host forms only: HMAC has no affine "
-            "shortcut, so a reframe is a full re-hash; composite and V2 batches of MAC ledgers are the "
-            "module-level package_batch_segments_mac / package_batch_v2_mac and their _host forms, which "
-            "take a key table")
+            "MAC ledgers have package_batch / verify_batch and their _host forms only: reframes, composite "
+            "and V2 batches of MAC ledgers are the module-level reframe_requests_mac, "
+            "package_batch_segments_mac / package_batch_v2_mac and their _host forms, which take a key table")
 
     reframe_batch = reframe_batch_host = _no_batch
     package_batch_segments = package_batch_segments_host = _no_batch

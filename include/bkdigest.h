@@ -726,6 +726,51 @@ BKD_API int bkd_digest_package_batch_ledgers_mac_host(const uint32_t* h_key_stat
                                                       const uint32_t* h_lengths, uint64_t n, void* h_frames,
                                                       uint64_t frame_stride);
 
+/* MAC reframe: re-replication of MAC ledgers (the flow of bkd_digest_reframe_batch above). HMAC has no
+ * affine shortcut, so a frame is hashed again; but the old and the new frame differ only in header bytes
+ * 16..23, so every 64-byte block behind the first is loaded, realigned and expanded once and compressed
+ * into two chains, one per header: verify and re-frame in one pass, one launch sequence and no host round
+ * trip. One ledger is one request; there is no single-ledger entry point.
+ *
+ * The key table, the CSR, d_req_flags, a key index >= nkeys, unreadable entries (out of range, over
+ * BKD_MAC_MAX_ENTRY), a malformed CSR, n == 0 and nreq == 0 exactly as in bkd_digest_verify_requests_mac.
+ * flags == 0: d_status, d_req_first_bad and the bounds flag are bit for bit those of
+ * bkd_digest_verify_requests_mac on the same input, and every entry whose status is BKD_VERIFY_OK is
+ * re-framed with d_new_lacs[i]. BKD_REFRAME_TRUSTED: the caller has verified these frames; only the MAC under
+ * the new header is computed, and the status is what the header alone decides: 1 too short, unreadable or
+ * no key row, else 3 / 4 by the id checks, never 2. Unlike the CRC trusted reframe, whose result for a
+ * frame with a wrong digest is wrong again, the MAC written is VALID for the bytes as they lie — a frame
+ * whose payload was damaged comes out verifying. The caller vouches for the bytes. Any other flag bit:
+ * BKD_ERR_INVALID_ARG.
+ * Output, OK entries only (no byte of any other entry's frame or out-frame is written):
+ *   apart    (d_out_frames != NULL): [32 B header with d_new_lacs[i]][20 B MAC] at d_out_frames +
+ *            i*frame_stride (frame_stride >= 52; only those 52 bytes are written; the range must not
+ *            overlap d_framed);
+ *   in place (d_out_frames == NULL, frame_stride == 0): bytes 16..23 and 32..51 of the frame itself. Frames
+ *            may start at any byte address and lie back to back; they must not overlap one another.
+ * Refused before any launch: a null array with n > 0, a null d_new_lacs, d_out_frames with frame_stride
+ * < 52, a frame_stride without d_out_frames. Device pointers; asynchronous on `stream`; no host
+ * synchronisation. */
+BKD_API int bkd_digest_reframe_requests_mac(
+    const uint32_t* d_key_states, uint64_t nkeys, const uint32_t* d_req_keys, uint32_t flags, void* d_framed,
+    uint64_t framed_size, const uint64_t* d_offsets, const uint32_t* d_lengths, uint64_t n, const uint64_t* d_req_first,
+    uint64_t nreq, const int64_t* d_req_ledger_ids, const int64_t* d_req_first_entry_ids, const uint32_t* d_req_flags,
+    const int64_t* d_new_lacs, void* d_out_frames, uint64_t frame_stride, int32_t* d_status, uint64_t* d_req_first_bad,
+    void* stream);
+/* Host-resident: entry i is its own writable host buffer h_frames[i], re-framed in place. Synchronous; the
+ * route as for the MAC host forms above. flags and h_new_lacs, then everything
+ * bkd_digest_verify_requests_mac_host checks, in its order, before any work: a violation returns
+ * BKD_ERR_INVALID_ARG and writes nothing. CPU: one frame per host task, the two chains over one schedule
+ * as on the device; no device needed. GPU: staged as bkd_digest_verify_requests_mac_host with the new LACs
+ * beside; the device writes packed 52-byte out-frames, which come back with the statuses, and the host
+ * writes bytes 16..23 and 32..51 of each OK frame. A request that straddles two staged segments gets the
+ * minimum of both parts as its prefix. */
+BKD_API int bkd_digest_reframe_requests_mac_host(
+    const uint32_t* h_key_states, uint64_t nkeys, const uint32_t* h_req_keys, uint32_t flags, void* const* h_frames,
+    const uint32_t* h_lengths, uint64_t n, const uint64_t* h_req_first, uint64_t nreq, const int64_t* h_req_ledger_ids,
+    const int64_t* h_req_first_entry_ids, const uint32_t* h_req_flags, const int64_t* h_new_lacs, int32_t* h_status,
+    uint64_t* h_req_first_bad);
+
 /* MAC adds: composite payloads and V2 add requests, the two add-path shapes of a MAC ledger behind a
  * Pulsar broker. Both span ledgers through the key table of bkd_digest_package_batch_ledgers_mac (one
  * ledger: a table of one row): entry i is keyed with row d_key_of[i] and framed for d_ledger_ids[i];
